@@ -11,9 +11,16 @@ in jets at the reference point and on the 64x64 (rho, z) grid (4097 points), the
 determinant and its scaled zero test are applied and the verdict bitmap + per-candidate
 outputs are written to HBM.  Inputs are resident in HBM before timing starts.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line (metric, value, unit, ms_per_step, ...); `--dump-outputs DIR` also writes
+the last timed step's outputs as DIR/<name>.npy.  Every other leg -- final verdicts and the
+gather, the plugin check, the per-pass profile and FP64 roofline, the Kerr sub-record, the
+early-exit / host-buffer / time-to-solutions legs, strict mode, the worker pool and the CPU
+baselines -- runs only with `--full` (minutes), where `--no-cpu` / `--no-extras` take legs away.
+
 Multi-GPU (torchrun, one process per GPU): the global batch (--n per rank) is cut into
 contiguous shards balanced by the programs' FLOP model (pdeval.shard); every rank validates its
-own shard (weak scaling, no data-path collective); after timing, one RCCL all-gather of the
+own shard (weak scaling, no data-path collective); after timing, with --full, one RCCL all-gather of the
 verdict bitmaps (pdeval_gather_bits, through the C ABI) assembles the global result on every
 rank, checked against torch.distributed's all-gather.
 """
@@ -159,9 +166,21 @@ def main():
     ap.add_argument('--parts', type=int, default=1, help='--strict-full: shares of the set')
     ap.add_argument('--plan-only', action='store_true',
                     help='print every rank\'s environment and shard plan as JSON and exit before any GPU call')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other leg: final verdicts + gather, '
+                         'plugin check, per-pass profile and rooflines, the Kerr sub-record, early-exit / '
+                         'host-buffer / time-to-solutions, strict mode, worker pool and the CPU baselines '
+                         '(minutes; --no-cpu / --no-extras take legs away again)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the device outputs of the last timed step (rank 0\'s shard; a fixed seed-0 '
+                         'sample of its rows when the batch is large) as DIR/<name>.npy, inf / NaN '
+                         'entries as 0 with their kind in DIR/<name>_nonfinite.npy')
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if not a.full:
+        # a plain run: set up, warm up, time the steps, dump, print the result line
+        a.no_cpu = a.no_extras = True
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and a.gpus > 1:
         # no launcher around us: start one rank process per GPU ourselves, before this process
@@ -218,17 +237,20 @@ def main():
     # RCCL through the C ABI (pdeval_gather_bits), checked against torch.distributed's.
     dev_out = pb.host_outputs()
     status_dev = dev_out['status'].copy()
-    if world > 1 or not a.no_extras:
+    if a.dump_outputs and rank == 0:
+        # before any later leg runs another step or a host step touches the arrays
+        log(f'outputs of the last timed step: {dump_outputs(a.dump_outputs, dev_out)}')
+    if a.full and (world > 1 or not a.no_extras):
         t0 = time.perf_counter()
         final = pb.final_verdicts(dev_out, prm)
         t_host = time.perf_counter() - t0
         log(f'final verdicts (host steps) {t_host:.2f} s')
         gather = {'bits': 'final (device + host steps)', 'host_steps_s': round(t_host, 3),
                   'host_step_changes_local': int((dev_out['status'] != status_dev).sum())}
-    else:   # (--no-extras at one GPU: timing runs, the device bitmap as it stands)
+    else:   # (a plain run, or --no-extras at one GPU: the device bitmap as it stands)
         final = status_dev == 0
-        gather = {'bits': 'device (--no-extras)'}
-    if world > 1:
+        gather = {'bits': 'device (--no-extras)' if a.full else 'device, this rank (no --full)'}
+    if a.full and world > 1:
         bits = torch.from_numpy(pack_bits(final)).to(dev)
         verdict_all = gather_verdicts(bits, ranges)
         try:
@@ -255,12 +277,13 @@ def main():
 
     # size-independent checks at full size: duplicates of one program (the batch is tiled)
     # get one class, and the streamable paper solutions are accepted wherever they occur
-    first = np.full(nprog, 255, dtype=np.int16)
-    first[idx[::-1]] = status_dev[::-1]
-    consistent = bool(np.array_equal(first[idx], status_dev))
-
-    prof = pb.profile(prm, a.steps)
-    log('per-pass profile')
+    consistent = prof = None
+    if a.full:
+        first = np.full(nprog, 255, dtype=np.int16)
+        first[idx[::-1]] = status_dev[::-1]
+        consistent = bool(np.array_equal(first[idx], status_dev))
+        prof = pb.profile(prm, a.steps)
+        log('per-pass profile')
 
     res = None
     if rank == 0:
@@ -276,16 +299,15 @@ def main():
                                    f'programs) tiled+shuffled(seed 0) to {a.n}/GPU; 64x64 grid + ref point',
                        'problem': a.problem, 'candidates_per_gpu': a.n, 'points_per_candidate': pb.npts,
                        'full_grid': not a.early_exit, 'parallelism': f'shard{world}'},
-            'roofline': prof['roofline'],
             'roofline_hbm': pb.roofline_hbm(kern_ms),
-            'pass_ms': prof['pass_ms'],
-            'work_lists': prof['counts'],
-            'accepted': int(verdict_all.sum()),
+            'accepted': int(verdict_all.sum()) if a.full or world == 1 else None,
             'accepted_device_bits': int((status_dev == 0).sum()) if world == 1 else None,
             'status_hist': np.bincount(status, minlength=8).tolist(),
-            'duplicates_consistent': consistent,
             'gather': gather,
         }
+        if a.full:
+            res.update(roofline=prof['roofline'], pass_ms=prof['pass_ms'], work_lists=prof['counts'],
+                       duplicates_consistent=consistent)
         if world > 1:
             res['shard_balance'] = 'flops'
         if not a.no_extras and world == 1 and pid == PROBLEM_FORCE_FREE:
@@ -531,6 +553,42 @@ class ProblemBench:
 
     def close(self):
         self.ctx.close()
+
+
+DUMP_ROWS = 1 << 18          # at most this many candidates' rows per dumped array (< 64 MB in all)
+
+
+def dump_outputs(out_dir, r):
+    """--dump-outputs: the arrays of ProblemBench.host_outputs (what a caller of the timed path
+    receives: status, verdict, q_ref, res_ref, q_grid, n_bad, n_nonfinite, fingerprint) as
+    <out_dir>/<name>.npy, float64 as they are and the integer / boolean ones as float32 (float64
+    for the int32 counts).  Every file holds finite numbers only, so that two dumps compare with
+    plain arithmetic: u of a candidate such as 1/(x - x) is inf or NaN at a fingerprint point, so
+    each float64 output <name> comes with <name>_nonfinite.npy of the same shape (float32: 0
+    finite, 1 +inf, 2 -inf, 3 NaN), and <name>.npy holds 0 where that code is not 0.  A batch of
+    more than DUMP_ROWS candidates is cut to a seed-0 sample of DUMP_ROWS rows in batch order,
+    the same rows in every array; the batch itself is tiled and shuffled with seed 0, so two
+    runs with the same arguments dump the same candidates."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(r['status'])
+    rows = np.arange(n)
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    files = {}
+    for name, arr in r.items():
+        arr = arr[rows]
+        if arr.dtype == np.float64:
+            code = np.zeros(arr.shape, dtype=np.float32)
+            code[arr == np.inf], code[arr == -np.inf], code[np.isnan(arr)] = 1, 2, 3
+            files[name + '_nonfinite'] = code
+            arr = np.where(code != 0, 0.0, arr)
+        else:
+            arr = arr.astype(np.float64 if arr.dtype.itemsize > 2 else np.float32)
+        files[name] = arr
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+    total = sum(arr.nbytes for arr in files.values())
+    return f'{len(files)} arrays, {len(rows)} of {n} rows, {total / 1e6:.1f} MB in {out_dir}'
 
 
 class _LazyItems:
