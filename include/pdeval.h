@@ -307,6 +307,32 @@ int pdeval_comm_init(pdeval_ctx* ctx, int world, int rank, const uint8_t* id);
 int pdeval_gather_bits(pdeval_ctx* ctx, const uint8_t* d_local, int64_t nbytes, uint8_t* d_global, void* stream);
 int pdeval_comm_destroy(pdeval_ctx* ctx);
 
+/* ---- foliation classes (force-free): the Jacobian match ----
+ * A force-free solution is a foliation, the level sets of u, and every f(u) is the same
+ * solution.  u and v belong to one class iff J = u_rho v_z - u_z v_rho vanishes on an m x m sample
+ * grid.  A field holds, per row, u_rho at the m * m sample points and then u_z: 2 m^2 doubles,
+ * NaN where u is not real and finite; the caller supplies the fields.  At a point with row
+ * gradient (a, b) and probe gradient (c, d): J = a d - b c, S = |a d| + |b c|; the point is
+ * usable iff J and S are finite and S > 0, and bad iff |J| > tau S (no division).  A row matches
+ * a probe iff n_used >= min_points and n_bad == 0.  The test does not involve the operator.  A
+ * Kerr context returns PDEVAL_ERR_ARG (its equation is linear: re-parametrisation is no
+ * symmetry there).                                                                           */
+typedef struct pdeval_fol_params {
+    double tau;          /* a usable point is bad iff |J| > tau * S (1e-7, the grid's tau_grid) */
+    int32_t m;           /* sample grid m x m, 4 <= m <= 64 (16)                                 */
+    int32_t min_points;  /* usable points a match needs (16)                                     */
+    int32_t reserved;
+} pdeval_fol_params;
+#define PDEVAL_FOL_MAX_PROBES 32
+int pdeval_default_fol_params(pdeval_fol_params* out);
+/* Device pointers, asynchronous on `stream` (NULL = the context's).  d_mask[row]: bit k set iff
+ * the row matches probe k; d_n_used, d_qmax (either may be NULL): n_rows x n_probe usable points
+ * and max |J| / S over them (a diagnostic; 0 without a usable point).  n_probe >
+ * PDEVAL_FOL_MAX_PROBES: PDEVAL_ERR_ARG.                                                      */
+int pdeval_jacobian_match(pdeval_ctx* ctx, const double* d_rows_field, int64_t n_rows,
+                          const double* d_probe_field, int n_probe, const pdeval_fol_params* params,
+                          uint32_t* d_mask, int32_t* d_n_used, double* d_qmax, void* stream);
+
 /* Host-side program analysis (no GPU): required stack depth, or < 0 if malformed.      */
 int pdeval_program_depth(const int32_t* ops, int64_t n_words);
 

@@ -23,6 +23,7 @@
 #include "pdeval_point.h"
 #include "pdeval_tier2.h"
 #include "pdeval_launch.h"
+#include "pdeval_foliation.h"
 
 using namespace pd;
 
@@ -1729,4 +1730,16 @@ extern "C" int pdeval_comm_destroy(pdeval_ctx* c) {
     c->world = 1;
     c->rank = 0;
     return PDEVAL_OK;
+}
+
+// ---- the context as the Jacobian match entry point sees it (pdeval_foliation.hip)
+void pd::fol_ctx(pdeval_ctx* c, FolCtx* v) {
+    v->problem = c->problem;
+    v->device = c->device;
+    v->stream = c->stream;
+}
+int pd::fol_fail(pdeval_ctx* c, int rc, const char* msg) {
+    if (c) c->err = msg;
+    else g_err = msg;
+    return rc;
 }

@@ -28,6 +28,7 @@ EXPORTS = (
     'pdeval_comm_unique_id', 'pdeval_comm_init', 'pdeval_gather_bits', 'pdeval_comm_destroy',
     'pdeval_default_kerr_constants', 'pdeval_set_kerr_constants', 'pdeval_compile_batch_mt',
     'pdeval_format_reasons', 'pdeval_device_error',
+    'pdeval_default_fol_params', 'pdeval_jacobian_match',
 )
 MAX_BATCH = 1 << 30          # PDEVAL_MAX_BATCH
 UNIQUE_ID_BYTES = 128
@@ -36,6 +37,7 @@ LIST_NAMES = ('defer_stack3', 'complex', 'defer_stack8', 'tier2', 'tier2_stack3'
               'point_dd_stack8', 'tier2_complex_stack8', 'grid_slow', 'grid_slow_stack3',
               'grid_slow_complex')
 N_PASSES = 12
+FOL_MAX_PROBES = 32          # PDEVAL_FOL_MAX_PROBES
 
 
 class Params(C.Structure):
@@ -62,6 +64,11 @@ class KerrConstants(C.Structure):
 
     def key(self):
         return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+class FolParams(C.Structure):
+    """pdeval_fol_params (include/pdeval.h): the Jacobian test on an m x m sample grid."""
+    _fields_ = [('tau', C.c_double), ('m', C.c_int32), ('min_points', C.c_int32), ('reserved', C.c_int32)]
 
 
 class PdevalError(RuntimeError):
@@ -116,6 +123,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_set_kerr_constants.argtypes = [vp, C.POINTER(KerrConstants)]
     for name in EXPORTS:
         getattr(lib, name)   # every symbol of the header must resolve
+    # (declared after the check: a stale library without them fails above, with the symbol's name)
+    lib.pdeval_default_fol_params.argtypes = [C.POINTER(FolParams)]
+    lib.pdeval_jacobian_match.argtypes = [vp, vp, i64, vp, C.c_int, C.POINTER(FolParams), vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -124,6 +134,12 @@ def load(path: Optional[str] = None) -> C.CDLL:
 def default_params(problem_id: int) -> Params:
     p = Params()
     _check(None, load().pdeval_default_params(problem_id, C.byref(p)))
+    return p
+
+
+def default_fol_params() -> FolParams:
+    p = FolParams()
+    _check(None, load().pdeval_default_fol_params(C.byref(p)))
     return p
 
 
@@ -286,6 +302,15 @@ class Context:
         w = C.c_uint32(0)
         _check(self.h, self.lib.pdeval_device_error(self.h, C.byref(w)))
         return int(w.value)
+
+    # ---- foliation classes (force-free; include/pdeval.h): the Jacobian match
+    def jacobian_match(self, d_rows: int, n_rows: int, d_probes: int, n_probe: int, d_mask: int,
+                       d_n_used: int = 0, d_qmax: int = 0, params: Optional[FolParams] = None, stream: int = 0):
+        """Device pointers, asynchronous: d_mask[row] bit k = row field matches probe field k
+        (n_probe <= 32); optionally n_used and qmax, n_rows x n_probe each."""
+        prm = params if params is not None else default_fol_params()
+        _check(self.h, self.lib.pdeval_jacobian_match(self.h, d_rows, n_rows, d_probes, n_probe, C.byref(prm),
+                                                      d_mask, d_n_used or None, d_qmax or None, stream or None))
 
 
 def comm_unique_id() -> bytes:
