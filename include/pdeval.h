@@ -39,6 +39,7 @@ extern "C" {
 #define PDEVAL_ERR_HIP         2   /* a HIP runtime call failed; see pdeval_last_error */
 #define PDEVAL_ERR_PROGRAM     3   /* a program failed host-side validation */
 #define PDEVAL_ERR_NODEVICE    4
+#define PDEVAL_ERR_ALLOC       5   /* a device allocation failed (pdeval_foliation_classes) */
 
 /* ---- problems (the problems/ plugin registry, problems/__init__.py:355-361) ---- */
 #define PDEVAL_PROBLEM_FORCE_FREE   0   /* foliation determinant, jets of order 4 */
@@ -311,7 +312,7 @@ int pdeval_comm_destroy(pdeval_ctx* ctx);
  * A force-free solution is a foliation, the level sets of u, and every f(u) is the same
  * solution.  u and v belong to one class iff J = u_rho v_z - u_z v_rho vanishes on an m x m sample
  * grid.  A field holds, per row, u_rho at the m * m sample points and then u_z: 2 m^2 doubles,
- * NaN where u is not real and finite; the caller supplies the fields.  At a point with row
+ * NaN where u is not real and finite (pdeval_gradient_fields builds them).  At a point with row
  * gradient (a, b) and probe gradient (c, d): J = a d - b c, S = |a d| + |b c|; the point is
  * usable iff J and S are finite and S > 0, and bad iff |J| > tau S (no division).  A row matches
  * a probe iff n_used >= min_points and n_bad == 0.  The test does not involve the operator.  A
@@ -332,6 +333,29 @@ int pdeval_default_fol_params(pdeval_fol_params* out);
 int pdeval_jacobian_match(pdeval_ctx* ctx, const double* d_rows_field, int64_t n_rows,
                           const double* d_probe_field, int n_probe, const pdeval_fol_params* params,
                           uint32_t* d_mask, int32_t* d_n_used, double* d_qmax, void* stream);
+/* The fields of programs resident in HBM (ops / offsets as pdeval_validate_device takes them):
+ * row r of d_field ([n_list][2][m^2]) is the field of candidate d_list[r] (d_list == NULL: rows
+ * 0 .. n_list-1 are candidates 0 .. n_list-1) at the m x m sample points of the context's grid,
+ * point p = i m + j at (xs[i], ys[j]), xs[i] = x_lo + (i + x_phase) (x_hi - x_lo) / m and likewise
+ * ys[j]: u_rho then u_z of the order-1 jet, both NaN unless u, u_rho and u_z are all finite.  The
+ * whole row is NaN for a program with PDEVAL_FLAG_COMPLEX, one the interpreter declines
+ * (malformed, unsupported opcode, stack deeper than PDEVAL_MAX_STACK), one whose offsets fall
+ * outside [0, n_words] or a list entry outside [0, n); such programs are never dereferenced.
+ * d_n_finite (may be NULL): per row, the points with a finite u_rho.  Asynchronous on `stream`
+ * (NULL = the context's).                                                                      */
+int pdeval_gradient_fields(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
+                           int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
+                           double* d_field, int32_t* d_n_finite, void* stream);
+/* The classes of the list, synchronous: computes the fields on the device (n_list x 2 m^2 x 8
+ * bytes, allocated for the call; PDEVAL_ERR_ALLOC if that fails), leaves rows with n_finite <
+ * min_points unclassified (leader -1) and groups the others in rounds: each round matches the
+ * still-unassigned rows against the first <= 32 of them on the device and downloads the masks
+ * only.  Row r joins the first-created leader it matches and otherwise becomes a leader.
+ * leader (host, n_list): the candidate index d_list[lead] of the row's leader; *n_classes,
+ * *n_rounds (either may be NULL): leaders created, rounds run.  The fields never reach the host. */
+int pdeval_foliation_classes(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
+                             int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
+                             int64_t* leader, int64_t* n_classes, int32_t* n_rounds);
 
 /* Host-side program analysis (no GPU): required stack depth, or < 0 if malformed.      */
 int pdeval_program_depth(const int32_t* ops, int64_t n_words);

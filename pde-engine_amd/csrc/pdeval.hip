@@ -1737,6 +1737,9 @@ void pd::fol_ctx(pdeval_ctx* c, FolCtx* v) {
     v->problem = c->problem;
     v->device = c->device;
     v->stream = c->stream;
+    const double g[8] = {c->grid.x_lo, c->grid.x_hi, c->grid.nx, c->grid.y_lo, c->grid.y_hi, c->grid.ny,
+                         c->grid.x_ph, c->grid.y_ph};
+    for (int i = 0; i < 8; ++i) v->grid[i] = g[i];
 }
 int pd::fol_fail(pdeval_ctx* c, int rc, const char* msg) {
     if (c) c->err = msg;

@@ -3,13 +3,13 @@
 // A force-free solution is a foliation, the level sets of u: every f(u) is the same solution.
 // Two candidates u and v describe the same foliation iff their gradients are parallel wherever
 // both exist, i.e. iff the Jacobian J = u_rho v_z - u_z v_rho vanishes identically.  The test
-// runs on gradient fields sampled on a small m x m grid: fol_match_kernel applies the scaled zero
-// test of J to rows of fields against up to 32 probe fields, and fol_round groups rows into
-// classes from the resulting masks.
+// runs on gradient fields sampled on a small m x m grid: fol_field_kernel computes them from the
+// resident programs, fol_match_kernel applies the scaled zero test of J to rows of fields against
+// up to 32 probe fields, and fol_round groups rows into classes from the resulting masks.
 //
-// This header holds the per-point test and the leader round, which also compile for the host
-// under -DPD_HOST_SIM (tests/hostsim/sim_foliation.cpp), the kernel's argument block and the
-// launcher of pdeval_foliation.hip.
+// This header holds the per-point code of both kernels and the leader round, which also compile
+// for the host under -DPD_HOST_SIM (tests/hostsim/sim_foliation.cpp, sim_foliation_field.cpp),
+// the kernels' argument blocks and the launchers of pdeval_foliation.hip.
 #pragma once
 #include <vector>
 
@@ -42,6 +42,81 @@ PD_HD FolPoint fol_point_test(double a, double b, double c, double d, double tau
 }
 // the diagnostic q = |J| / S of a usable point (IEEE division)
 PD_HD double fol_q(const FolPoint& r) { return fabs(r.J) / r.S; }
+
+// ---------------------------------------------------------------- the gradient field (host + device)
+// The field of a program: (u_rho, u_z) of its order-1 jet at the m x m sample points of the
+// context's grid, point p = i m + j at (xs[i], ys[j]), xs[i] = x_lo + (i + x_phase) dx,
+// dx = (x_hi - x_lo) / m (rounded on the host), and likewise for y.
+struct FolGrid {
+    double x_lo, dx, x_ph, y_lo, dy, y_ph;
+    int m;
+};
+PD_HD FolGrid fol_grid(const double* g, int m) {   // g: the context's 8 grid doubles
+    return {g[0], (g[1] - g[0]) / m, g[6], g[3], (g[4] - g[3]) / m, g[7], m};
+}
+// the coordinates of point p < m^2: product and sum rounded separately, as the restatement does
+PD_HD void fol_point_xy(const FolGrid& g, int p, double& x, double& y) {
+#pragma clang fp contract(off)
+    const int i = p / g.m, j = p - i * g.m;
+    const double tx = ((double)i + g.x_ph) * g.dx, ty = ((double)j + g.y_ph) * g.dy;
+    x = g.x_lo + tx;
+    y = g.y_lo + ty;
+}
+
+// Every stack depth up to PDEVAL_MAX_STACK in one instantiation: with the
+// operand stack in LDS the depth costs no registers, only (MAXD - 1) x 3 x 64 doubles per wave.
+constexpr int kFolMaxD = PDEVAL_MAX_STACK;
+constexpr int kFolStackDoubles = (kFolMaxD - 1) * nc(1) * 64;   // per wave
+using FolInterp = Interp<double, 1, kFolMaxD>;
+
+// The program of list row `row`, wave-uniform.  ok = false -- the whole row is NaN and no
+// program word is read -- when the list entry lies outside [0, n) or the candidate's
+// [offsets[c], offsets[c + 1]) does not lie inside [0, n_words]; otherwise the header word is
+// read, and ok = false for a complex program, a non-header first word or a stack deeper than
+// kFolMaxD.
+struct FolProg {
+    const int32_t* words;
+    int len;
+    bool ok;
+};
+__device__ __forceinline__ FolProg fol_program(const int32_t* ops, int64_t n_words, const int64_t* offsets,
+                                               int64_t n, const int64_t* list, int64_t row) {
+    FolProg r{ops, 0, false};
+    const int64_t cand = list ? list[row] : row;
+    if (cand < 0 || cand >= n) return r;
+    const int64_t beg = offsets[cand], end = offsets[cand + 1];
+    if (!(beg >= 0 && end > beg && end <= n_words && end - beg < (1 << 24))) return r;
+    r.words = ops + beg;
+    r.len = (int)(end - beg);
+    const uint32_t hdr = rd_word(r.words);
+    r.ok = (hdr & 0xffu) == 0u && !(hdr & PDEVAL_FLAG_COMPLEX) && (int)((hdr >> 8) & 0xffu) <= kFolMaxD;
+    return r;
+}
+
+// One sample point of an ok program: rc = the interpreter's result (wave-uniform; anything but
+// RUN_OK makes the whole row NaN), (a, b) = (u_rho, u_z), both NaN unless u, u_rho and u_z are all
+// finite; fin = u_rho is finite (what n_finite counts).  P: the problem's constants, a default
+// table (force-free programs carry none).  The kernel takes it from its arguments, in scalar
+// registers: a table local to the kernel, indexed by a program word, cost 64 bytes of scratch.
+struct FolField {
+    double a, b;
+    bool fin;
+    int rc;
+};
+__device__ __forceinline__ FolField fol_field_point(const FolProg& pr, const FolGrid& g, int p, double* stk, int lane,
+                                                    const PrmTab<double>& P) {
+    double x, y;
+    fol_point_xy(g, p, x, y);
+    FolInterp::J u;
+    FolField f;
+    f.rc = FolInterp::run(pr.words, 1, pr.len, x, y, u, stk, lane, P);
+    const bool ok = f.rc == RUN_OK && finite_(u.c[0]) && finite_(u.c[ji(1, 0)]) && finite_(u.c[ji(0, 1)]);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    f.a = ok ? u.c[ji(1, 0)] : nan;
+    f.b = ok ? u.c[ji(0, 1)] : nan;
+    f.fin = ok;
+    return f;
+}
 
 // ---------------------------------------------------------------- the leader rule (host)
 // One round of the grouping.  un: the nu still-unassigned rows in list order, the
@@ -90,13 +165,33 @@ struct FolMatchArgs {
     uint32_t* mask;            // n_rows
     int32_t* n_used;           // optional, n_rows x n_probe
     double* qmax;              // optional, n_rows x n_probe
+    // optional (pdeval_foliation_classes: the unassigned subset of a round, its first rows the
+    // probes): row r's field is rows[idx[r]], probe k's is probes[pidx[k]]; NULL = r, k
+    const int64_t* idx;
+    const int64_t* pidx;
 };
 void launch_fol_match(const FolMatchArgs& a, hipStream_t s);
+
+struct FolFieldArgs {
+    const int32_t* ops;
+    int64_t n_words;
+    const int64_t* offsets;
+    int64_t n;
+    const int64_t* list;       // optional: row -> candidate index (NULL = identity)
+    int64_t n_list;
+    int n_chunk;               // ceil(m^2 / 64)
+    FolGrid grid;
+    PrmTab<double> prm;        // default (all 0): force-free programs carry no problem constants
+    double* field;             // [n_list][2][m^2]
+    int32_t* n_finite;         // optional, n_list, zeroed by the caller
+};
+void launch_fol_field(const FolFieldArgs& a, hipStream_t s);
 
 // what the entry point (pdeval_foliation.hip) needs of a context (pdeval.hip)
 struct FolCtx {
     int problem, device;
     hipStream_t stream;
+    double grid[8];   // {x_lo, x_hi, nx, y_lo, y_hi, ny, x_phase, y_phase} (pdeval_create)
 };
 void fol_ctx(pdeval_ctx* c, FolCtx* out);
 // records msg as the context's pdeval_last_error text (the thread's when c is NULL); returns rc

@@ -28,7 +28,7 @@ EXPORTS = (
     'pdeval_comm_unique_id', 'pdeval_comm_init', 'pdeval_gather_bits', 'pdeval_comm_destroy',
     'pdeval_default_kerr_constants', 'pdeval_set_kerr_constants', 'pdeval_compile_batch_mt',
     'pdeval_format_reasons', 'pdeval_device_error',
-    'pdeval_default_fol_params', 'pdeval_jacobian_match',
+    'pdeval_default_fol_params', 'pdeval_jacobian_match', 'pdeval_gradient_fields', 'pdeval_foliation_classes',
 )
 MAX_BATCH = 1 << 30          # PDEVAL_MAX_BATCH
 UNIQUE_ID_BYTES = 128
@@ -126,6 +126,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     # (declared after the check: a stale library without them fails above, with the symbol's name)
     lib.pdeval_default_fol_params.argtypes = [C.POINTER(FolParams)]
     lib.pdeval_jacobian_match.argtypes = [vp, vp, i64, vp, C.c_int, C.POINTER(FolParams), vp, vp, vp, vp]
+    lib.pdeval_gradient_fields.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), vp, vp, vp]
+    lib.pdeval_foliation_classes.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -311,6 +313,25 @@ class Context:
         prm = params if params is not None else default_fol_params()
         _check(self.h, self.lib.pdeval_jacobian_match(self.h, d_rows, n_rows, d_probes, n_probe, C.byref(prm),
                                                       d_mask, d_n_used or None, d_qmax or None, stream or None))
+
+    def gradient_fields(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int,
+                        d_field: int, d_n_finite: int = 0, params: Optional[FolParams] = None, stream: int = 0):
+        """Device pointers, asynchronous: d_field[r] = the [2, m*m] field (u_rho, u_z) of candidate
+        d_list[r] (d_list = 0: candidate r) of the resident programs; optionally n_finite per row."""
+        prm = params if params is not None else default_fol_params()
+        _check(self.h, self.lib.pdeval_gradient_fields(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
+                                                       C.byref(prm), d_field, d_n_finite or None, stream or None))
+
+    def foliation_classes(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int,
+                          params: Optional[FolParams] = None):
+        """Synchronous: (leader int64[n_list], n_classes, n_rounds) of the listed candidates of the
+        resident programs; leader[r] = the candidate index of row r's class leader, -1 unclassified."""
+        prm = params if params is not None else default_fol_params()
+        leader = np.full(max(n_list, 0), -1, dtype=np.int64)
+        ncls, nrnd = C.c_int64(0), C.c_int32(0)
+        _check(self.h, self.lib.pdeval_foliation_classes(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
+                                                         C.byref(prm), _ptr(leader), C.byref(ncls), C.byref(nrnd)))
+        return leader, int(ncls.value), int(nrnd.value)
 
 
 def comm_unique_id() -> bytes:

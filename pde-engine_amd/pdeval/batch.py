@@ -824,6 +824,30 @@ class BatchValidator:
         ops, off, notes = compile_strings(self.pd, list(strings), stats=stats)
         return self._verdicts(ops, off, notes, list(strings), symbolic, symbolic_timeout)
 
+    def foliation_classes(self, strings: Sequence[str], params=None):
+        """The foliation classes of the accepted candidates among ``strings`` (force-free; DESIGN.md
+        §14): compiles and validates them, uploads the programs once and classifies the rows the
+        device accepted (``CLS_ACCEPT``, before any host step) with ``pdeval.foliation.classify``.
+        Returns ``(classes, accepted, tags)``: the ``FoliationClasses`` over the accepted rows
+        (``leader`` holds indices into ``strings``), the accepted indices, and ``{class_id: name}``
+        of the classes that re-parametrise a known solution (``pdeval.foliation.tag_known``)."""
+        if self.pd.problem_id != PROBLEM_FORCE_FREE:
+            raise ValueError('foliation classes are a force-free notion (the Kerr equation is linear: '
+                             'u -> f(u) is no symmetry of it)')
+        import torch
+        from . import foliation as F
+        from .native import compile_strings
+        ops, off, _ = compile_strings(self.pd, list(strings))
+        accepted = np.flatnonzero(np.asarray(self.run(ops, off)['status']) == CLS_ACCEPT).astype(np.int64)
+        dev = torch.device('cuda', self.device)
+        d_ops = torch.from_numpy(np.ascontiguousarray(ops, dtype=np.int32)).to(dev)
+        d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64)).to(dev)
+        n, n_words = len(off) - 1, int(d_ops.numel())
+        with self._lock:
+            classes = F.classify(self.ctx, d_ops, n_words, d_off, n, accepted, params)
+            tags = F.tag_known(self.ctx, self.pd, classes, (d_ops, n_words, d_off, n), params)
+        return classes, accepted, tags
+
     def close(self):
         self.ctx.close()
 
