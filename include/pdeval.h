@@ -357,6 +357,61 @@ int pdeval_foliation_classes(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_wo
                              int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
                              int64_t* leader, int64_t* n_classes, int32_t* n_rounds);
 
+/* ---- foliation class registry (DESIGN.md §14 "Registry"): classes across batches ----
+ * A registry keeps the class leaders' gradient fields resident on the device, so a stream of
+ * batches is classified as one list: the sequential rule above over the concatenation of all
+ * batches in the order they were assigned.  Per batch, Stage A tests every row against the
+ * resident leaders 0 .. L-1 in creation order (fol_assign_kernel: one launch and one download
+ * whatever L is) and gives it the id of the first it matches; Stage B groups the rows Stage A
+ * leaves unmatched (and that have >= min_points finite points) among themselves by the rounds of
+ * pdeval_foliation_classes; their leaders get the ids L, L+1, ... in list order and their fields
+ * are appended.  Class ids are dense, in order of creation, and never change; a row with fewer
+ * than min_points finite points gets -1.  Assigning a list in any number of consecutive batches
+ * gives the classes pdeval_foliation_classes gives on the whole list.  The limit of the
+ * definition is inherited: a function of one coordinate matches nothing, not even itself, so
+ * every such row is a leader.
+ * A registry is bound to the force-free context and the parameters it was created with; every
+ * call that runs on the device takes that context and returns PDEVAL_ERR_ARG for another one.
+ * The calls are synchronous, on the context's stream.  The leader store grows by doubling
+ * (capacity_hint: leaders to make room for at creation, 0 = 1); PDEVAL_ERR_ALLOC leaves the
+ * registry unchanged.  The store is chunk-major (the 64-point chunks of consecutive leaders are
+ * contiguous), not [L][2][m^2]: pdeval_fol_registry_leaders writes the fields out in that order.
+ * Destroy a registry before its context.                                                       */
+typedef struct pdeval_fol_registry pdeval_fol_registry;
+int pdeval_fol_registry_create(pdeval_ctx* ctx, const pdeval_fol_params* params /* NULL = default */,
+                               int64_t capacity_hint, pdeval_fol_registry** out);
+int pdeval_fol_registry_destroy(pdeval_fol_registry* reg);
+/* The listed candidates of programs resident in HBM (as pdeval_gradient_fields takes them): the
+ * field kernel, then pdeval_fol_registry_assign_fields.  keys (host, n_list, may be NULL): the
+ * caller's identifier of each row, kept for the rows that become leaders; NULL = the running row
+ * number over all calls.  class_id (host, n_list): the rows' class ids; *n_new (may be NULL):
+ * leaders created by the call.  n_list == 0 is OK and changes nothing.                        */
+int pdeval_fol_registry_assign(pdeval_ctx* ctx, pdeval_fol_registry* reg, const int32_t* d_ops, int64_t n_words,
+                               const int64_t* d_offsets, int64_t n, const int64_t* d_list, int64_t n_list,
+                               const int64_t* keys, int64_t* class_id, int64_t* n_new);
+/* The same on fields the caller holds: d_fields [n_rows][2][m^2] (device), d_n_finite (device,
+ * n_rows, may be NULL: counted here) the points of each row with a finite u_rho.               */
+int pdeval_fol_registry_assign_fields(pdeval_ctx* ctx, pdeval_fol_registry* reg, const double* d_fields,
+                                      const int32_t* d_n_finite, int64_t n_rows, const int64_t* keys,
+                                      int64_t* class_id, int64_t* n_new);
+int pdeval_fol_registry_size(pdeval_fol_registry* reg, int64_t* n_classes, int64_t* n_rows_seen);
+/* Any argument may be NULL.  d_fields: a caller's device buffer of n_classes x 2 m^2 doubles that
+ * receives the leaders' fields in [L][2][m^2] order (the store itself is chunk-major);
+ * leader_keys, sizes (host, n_classes): each class's key and number of rows.                   */
+int pdeval_fol_registry_leaders(pdeval_fol_registry* reg, double* d_fields, int64_t* leader_keys, int64_t* sizes);
+/* Installs saved leaders (d_fields [n_classes][2][m^2] on the device, keys and sizes on the host)
+ * as they are, without re-matching, so their ids are preserved.  Only into an empty registry:
+ * otherwise PDEVAL_ERR_ARG.  The count of rows seen restarts at the sum of the sizes.          */
+int pdeval_fol_registry_load(pdeval_ctx* ctx, pdeval_fol_registry* reg, const double* d_fields,
+                             const int64_t* leader_keys, const int64_t* sizes, int64_t n_classes);
+/* Any argument may be NULL.  params: the registry's; grid: the 8 grid doubles of its context
+ * {x_lo, x_hi, nx, y_lo, y_hi, ny, x_phase, y_phase}; *stage_a_ms: the device time of Stage A's
+ * launch in the most recent assign call (HIP events; 0 if it launched none).                   */
+int pdeval_fol_registry_info(pdeval_fol_registry* reg, pdeval_fol_params* params, double* grid, double* stage_a_ms);
+/* count[k] rows more in class class_id[k] (host arrays of n), rows that were classified
+ * elsewhere: how the sizes of a merged registry are carried over.                              */
+int pdeval_fol_registry_add_sizes(pdeval_fol_registry* reg, const int64_t* class_id, const int64_t* count, int64_t n);
+
 /* Host-side program analysis (no GPU): required stack depth, or < 0 if malformed.      */
 int pdeval_program_depth(const int32_t* ops, int64_t n_words);
 

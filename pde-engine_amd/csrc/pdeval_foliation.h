@@ -5,7 +5,9 @@
 // both exist, i.e. iff the Jacobian J = u_rho v_z - u_z v_rho vanishes identically.  The test
 // runs on gradient fields sampled on a small m x m grid: fol_field_kernel computes them from the
 // resident programs, fol_match_kernel applies the scaled zero test of J to rows of fields against
-// up to 32 probe fields, and fol_round groups rows into classes from the resulting masks.
+// up to 32 probe fields, and fol_round groups rows into classes from the resulting masks.  A
+// registry (pdeval_fol_registry.hip) keeps the leaders' fields on the device across batches:
+// fol_assign_kernel finds each row's first match among them (fol_chunk_test, fol_store_at).
 //
 // This header holds the per-point code of both kernels and the leader round, which also compile
 // for the host under -DPD_HOST_SIM (tests/hostsim/sim_foliation.cpp, sim_foliation_field.cpp),
@@ -152,6 +154,31 @@ inline int fol_round(const uint32_t* mask, const int64_t* un, int64_t nu, int np
     return created;
 }
 
+// ---------------------------------------------------------------- the registry's pair scan (host + device)
+// The leader store of a registry is chunk-major: chunk c (64 sample points) of leader l is the
+// 128 doubles at fol_store_at(cap, c, l) -- u_rho of points 64 c .. 64 c + 63, then u_z -- so the
+// first chunk of consecutive leaders, which decides almost every non-matching pair, is one
+// contiguous run, and the later chunks are touched only by the pairs that survive it.  Points
+// past m^2 in the last chunk hold NaN.
+constexpr int kFolChunk = 64;
+constexpr int kFolAssignTile = 32;   // leaders per LDS tile of fol_assign_kernel (T)
+constexpr int kFolRegChunks = 4;     // chunks of a row held in registers: m <= 16
+PD_HD int64_t fol_store_at(int64_t cap, int chunk, int64_t leader) {
+    return ((int64_t)chunk * cap + leader) * (2 * kFolChunk);
+}
+// One chunk of a (row, leader) pair: this lane's point added to the pair's wave-uniform counts
+// by fol_point_test and a ballot each (one lane under PD_HOST_SIM).  A pair is left at the first
+// chunk with nb != 0; it matches iff nu >= min_points and nb == 0 after its last chunk.
+struct FolCount {
+    int nu, nb;
+};
+__device__ __forceinline__ void fol_chunk_test(double a, double b, double c, double d, bool active, double tau,
+                                               FolCount& n) {
+    const FolPoint t = fol_point_test(a, b, c, d, tau);
+    n.nu += count_lanes(active && t.used);
+    n.nb += count_lanes(active && t.bad);
+}
+
 #ifndef PD_HOST_SIM
 // ---------------------------------------------------------------- kernel arguments, launcher
 struct FolMatchArgs {
@@ -187,7 +214,38 @@ struct FolFieldArgs {
 };
 void launch_fol_field(const FolFieldArgs& a, hipStream_t s);
 
-// what the entry point (pdeval_foliation.hip) needs of a context (pdeval.hip)
+// Stage A of a registry (pdeval_fol_registry.hip): first[row] = the smallest leader index the row
+// matches, -1 if none (or n_finite[row] < min_points, when given)
+struct FolAssignArgs {
+    const double* rows;        // row fields, [n_rows][2][mm]
+    int64_t n_rows;
+    const int32_t* n_finite;   // optional, n_rows
+    const double* store;       // the leader store, chunk-major (fol_store_at)
+    int64_t cap, L;            // its capacity and the leaders it holds
+    int mm, n_chunk;
+    double tau;
+    int min_points;
+    int64_t* first;            // n_rows
+};
+void launch_fol_assign(const FolAssignArgs& a, hipStream_t s);
+
+// rows of [.][2][mm] fields into the store (append, load) or the store's leaders out to
+// [L][2][mm] (leaders): one wave per (leader, chunk)
+struct FolMoveArgs {
+    double* store;
+    int64_t cap, base;         // leader k of the call is store leader base + k
+    int64_t n_lead;
+    double* fields;            // [n_rows][2][mm]
+    int64_t n_rows;
+    const int64_t* idx;        // optional: leader k's field is fields[idx[k]] (checked against n_rows)
+    int mm, n_chunk;
+    int to_store;              // 1: fields -> store, 0: store -> fields
+};
+void launch_fol_move(const FolMoveArgs& a, hipStream_t s);
+// n_finite[row] = the points of the row with a finite u_rho (fields the caller holds)
+void launch_fol_nfinite(const double* fields, int64_t n_rows, int mm, int32_t* n_finite, hipStream_t s);
+
+// what the entry points (pdeval_foliation.hip, pdeval_fol_registry.hip) need of a context (pdeval.hip)
 struct FolCtx {
     int problem, device;
     hipStream_t stream;
@@ -196,6 +254,22 @@ struct FolCtx {
 void fol_ctx(pdeval_ctx* c, FolCtx* out);
 // records msg as the context's pdeval_last_error text (the thread's when c is NULL); returns rc
 int fol_fail(pdeval_ctx* c, int rc, const char* msg);
+
+// shared by the entry points of pdeval_foliation.hip and pdeval_fol_registry.hip
+// the checks of the program entry points; fills prm and the context view
+int fol_check(pdeval_ctx* c, const char* fn, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
+              int64_t n, int64_t n_list, const pdeval_fol_params* params, FolCtx* v, pdeval_fol_params* prm);
+int fol_hip_fail(pdeval_ctx* c, const char* what, hipError_t e);
+// zeroes d_n_finite (if given) and launches the field kernel on s
+int fol_fields_launch(pdeval_ctx* c, const FolCtx& v, const pdeval_fol_params& prm, const int32_t* d_ops,
+                      int64_t n_words, const int64_t* d_offsets, int64_t n, const int64_t* d_list, int64_t n_list,
+                      double* d_field, int32_t* d_n_finite, hipStream_t s);
+// The rounds: groups the rows `un` (indices into d_field's rows, in list order; emptied) with
+// fol_match_kernel and fol_round, d_idx / d_mask holding un.size() entries each.  leader[row]
+// receives list[leader row] (the row itself without a list).  Synchronizes s once per round.
+int fol_rounds(pdeval_ctx* c, const double* d_field, int mm, const pdeval_fol_params& prm, std::vector<int64_t>& un,
+               const int64_t* list, int64_t* leader, int64_t* d_idx, uint32_t* d_mask, hipStream_t s,
+               int64_t* classes, int32_t* rounds);
 #endif  // PD_HOST_SIM
 
 }  // namespace pd

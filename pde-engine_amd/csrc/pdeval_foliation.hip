@@ -154,8 +154,8 @@ extern "C" int pdeval_jacobian_match(pdeval_ctx* c, const double* d_rows_field, 
     return PDEVAL_OK;
 }
 
-namespace {
-// the checks the two program entry points share; fills prm and the context view
+namespace pd {
+// the checks the program entry points share; fills prm and the context view
 int fol_check(pdeval_ctx* c, const char* fn, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
               int64_t n, int64_t n_list, const pdeval_fol_params* params, FolCtx* v, pdeval_fol_params* prm) {
     const std::string f(fn);
@@ -204,7 +204,44 @@ int fol_fields_launch(pdeval_ctx* c, const FolCtx& v, const pdeval_fol_params& p
     if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_field_kernel", e);
     return PDEVAL_OK;
 }
-}  // namespace
+
+// the rounds of pdeval_foliation_classes and of a registry's Stage B
+int fol_rounds(pdeval_ctx* c, const double* d_field, int mm, const pdeval_fol_params& prm, std::vector<int64_t>& un,
+               const int64_t* list, int64_t* leader, int64_t* d_idx, uint32_t* d_mask, hipStream_t s,
+               int64_t* classes, int32_t* rounds) {
+    hipError_t e;
+    std::vector<int64_t> next;
+    std::vector<uint32_t> mask;
+    while (!un.empty()) {
+        const int64_t nu = (int64_t)un.size();
+        const int np = (int)std::min<int64_t>(PDEVAL_FOL_MAX_PROBES, nu);
+        mask.resize((size_t)nu);
+        if ((e = hipMemcpyAsync(d_idx, un.data(), (size_t)nu * sizeof(int64_t), hipMemcpyHostToDevice, s)) != hipSuccess)
+            return fol_hip_fail(c, "hipMemcpyAsync", e);
+        FolMatchArgs a{};
+        a.rows = d_field;
+        a.n_rows = nu;
+        a.probes = d_field;
+        a.n_probe = np;
+        a.mm = mm;
+        a.tau = prm.tau;
+        a.min_points = prm.min_points;
+        a.mask = d_mask;
+        a.idx = d_idx;
+        a.pidx = d_idx;   // the round's probes: its first np rows
+        launch_fol_match(a, s);
+        if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_match_kernel", e);
+        if ((e = hipMemcpyAsync(mask.data(), d_mask, (size_t)nu * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+            return fol_hip_fail(c, "hipMemcpyAsync", e);
+        // (un is read by the upload above until the stream has passed it: synchronize before fol_round swaps it)
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "fol_match_kernel", e);
+        *classes += fol_round(mask.data(), un.data(), nu, np, list, leader, next);
+        un.swap(next);
+        ++*rounds;
+    }
+    return PDEVAL_OK;
+}
+}  // namespace pd
 
 extern "C" int pdeval_gradient_fields(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
                                       int64_t n, const int64_t* d_list, int64_t n_list,
@@ -285,40 +322,17 @@ extern "C" int pdeval_foliation_classes(pdeval_ctx* c, const int32_t* d_ops, int
         return hip_fail("hipMemcpyAsync", e);
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("fol_field_kernel", e);
     // rows with too few finite points are unclassified; the others wait for a round
-    std::vector<int64_t> un, next;
+    std::vector<int64_t> un;
     for (int64_t r = 0; r < n_list; ++r) {
         leader[r] = -1;
         if (nfin[(size_t)r] >= prm.min_points) un.push_back(r);
     }
-    std::vector<uint32_t> mask;
     int64_t classes = 0;
     int32_t rounds = 0;
-    while (!un.empty()) {
-        const int64_t nu = (int64_t)un.size();
-        const int np = (int)std::min<int64_t>(PDEVAL_FOL_MAX_PROBES, nu);
-        mask.resize((size_t)nu);
-        if ((e = hipMemcpyAsync(d_idx, un.data(), (size_t)nu * sizeof(int64_t), hipMemcpyHostToDevice, s)) != hipSuccess)
-            return hip_fail("hipMemcpyAsync", e);
-        FolMatchArgs a{};
-        a.rows = d_field;
-        a.n_rows = nu;
-        a.probes = d_field;
-        a.n_probe = np;
-        a.mm = mm;
-        a.tau = prm.tau;
-        a.min_points = prm.min_points;
-        a.mask = d_mask;
-        a.idx = d_idx;
-        a.pidx = d_idx;   // the round's probes: its first np rows
-        launch_fol_match(a, s);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("fol_match_kernel", e);
-        if ((e = hipMemcpyAsync(mask.data(), d_mask, (size_t)nu * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
-            return hip_fail("hipMemcpyAsync", e);
-        // (un is read by the upload above until the stream has passed it: synchronize before fol_round swaps it)
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("fol_match_kernel", e);
-        classes += fol_round(mask.data(), un.data(), nu, np, d_list ? list.data() : nullptr, leader, next);
-        un.swap(next);
-        ++rounds;
+    rc = fol_rounds(c, d_field, mm, prm, un, d_list ? list.data() : nullptr, leader, d_idx, d_mask, s, &classes, &rounds);
+    if (rc != PDEVAL_OK) {
+        release();
+        return rc;
     }
     release();
     if (n_classes) *n_classes = classes;

@@ -29,6 +29,9 @@ EXPORTS = (
     'pdeval_default_kerr_constants', 'pdeval_set_kerr_constants', 'pdeval_compile_batch_mt',
     'pdeval_format_reasons', 'pdeval_device_error',
     'pdeval_default_fol_params', 'pdeval_jacobian_match', 'pdeval_gradient_fields', 'pdeval_foliation_classes',
+    'pdeval_fol_registry_create', 'pdeval_fol_registry_destroy', 'pdeval_fol_registry_assign',
+    'pdeval_fol_registry_assign_fields', 'pdeval_fol_registry_size', 'pdeval_fol_registry_leaders',
+    'pdeval_fol_registry_load', 'pdeval_fol_registry_info', 'pdeval_fol_registry_add_sizes',
 )
 MAX_BATCH = 1 << 30          # PDEVAL_MAX_BATCH
 UNIQUE_ID_BYTES = 128
@@ -128,6 +131,16 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_jacobian_match.argtypes = [vp, vp, i64, vp, C.c_int, C.POINTER(FolParams), vp, vp, vp, vp]
     lib.pdeval_gradient_fields.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), vp, vp, vp]
     lib.pdeval_foliation_classes.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), vp, vp, vp]
+    # the foliation class registry (ctx, registry, ...)
+    lib.pdeval_fol_registry_create.argtypes = [vp, C.POINTER(FolParams), i64, C.POINTER(vp)]
+    lib.pdeval_fol_registry_destroy.argtypes = [vp]
+    lib.pdeval_fol_registry_assign.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, C.POINTER(i64)]
+    lib.pdeval_fol_registry_assign_fields.argtypes = [vp, vp, vp, vp, i64, vp, vp, C.POINTER(i64)]
+    lib.pdeval_fol_registry_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.pdeval_fol_registry_leaders.argtypes = [vp, vp, vp, vp]
+    lib.pdeval_fol_registry_load.argtypes = [vp, vp, vp, vp, vp, i64]
+    lib.pdeval_fol_registry_info.argtypes = [vp, C.POINTER(FolParams), vp, C.POINTER(dbl)]
+    lib.pdeval_fol_registry_add_sizes.argtypes = [vp, vp, vp, i64]
     if path is None:
         _lib = lib
     return lib
@@ -332,6 +345,12 @@ class Context:
         _check(self.h, self.lib.pdeval_foliation_classes(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
                                                          C.byref(prm), _ptr(leader), C.byref(ncls), C.byref(nrnd)))
         return leader, int(ncls.value), int(nrnd.value)
+
+    def fol_registry(self, params: Optional[FolParams] = None, capacity_hint: int = 0):
+        """A ``pdeval.foliation.FoliationRegistry`` on this context: the class leaders' fields
+        resident on the device across batches (pdeval_fol_registry_*)."""
+        from .foliation import FoliationRegistry
+        return FoliationRegistry(self, params, capacity_hint)
 
 
 def comm_unique_id() -> bytes:

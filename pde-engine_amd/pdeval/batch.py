@@ -848,6 +848,42 @@ class BatchValidator:
             tags = F.tag_known(self.ctx, self.pd, classes, (d_ops, n_words, d_off, n), params)
         return classes, accepted, tags
 
+    def foliation_registry(self, params=None, capacity_hint: int = 0):
+        """A ``pdeval.foliation.FoliationRegistry`` on this validator's context (force-free): the
+        streaming caller holds it next to the validator and passes it to ``assign_foliation``."""
+        if self.pd.problem_id != PROBLEM_FORCE_FREE:
+            raise ValueError('foliation classes are a force-free notion (the Kerr equation is linear: '
+                             'u -> f(u) is no symmetry of it)')
+        with self._lock:
+            return self.ctx.fol_registry(params, capacity_hint)
+
+    def assign_foliation(self, registry, strings: Sequence[str], keys=None):
+        """One batch of a stream into ``registry`` (``foliation_registry``): compiles and validates
+        ``strings``, uploads the programs once and assigns the rows the device accepted
+        (``CLS_ACCEPT``, before any host step).  ``keys`` (one per string, optional): the caller's
+        identifiers; the accepted rows' keys go to the registry.  Returns ``(class_id_of_accepted,
+        accepted_idx)``: the registry's class ids of the accepted rows and their indices into
+        ``strings``."""
+        if registry.ctx is not self.ctx:
+            raise ValueError('assign_foliation: the registry belongs to another validator\'s context')
+        import torch
+        from .native import compile_strings
+        if not strings:
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        ops, off, _ = compile_strings(self.pd, list(strings))
+        accepted = np.flatnonzero(np.asarray(self.run(ops, off)['status']) == CLS_ACCEPT).astype(np.int64)
+        if keys is not None:
+            keys = np.asarray(keys, dtype=np.int64)
+            if keys.shape != (len(strings),):
+                raise ValueError(f'keys: expected {len(strings)} entries, got shape {keys.shape}')
+            keys = keys[accepted]
+        dev = torch.device('cuda', self.device)
+        d_ops = torch.from_numpy(np.ascontiguousarray(ops, dtype=np.int32)).to(dev)
+        d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64)).to(dev)
+        with self._lock:
+            cls = registry.assign(d_ops, int(d_ops.numel()), d_off, len(off) - 1, accepted, keys)
+        return cls, accepted
+
     def close(self):
         self.ctx.close()
 

@@ -7,7 +7,8 @@ classes of accepted candidates from programs resident on the device (fields, mat
 stay there), :func:`tag_known` names the classes that are re-parametrisations of a paper
 solution, :func:`gradient_fields` returns the fields themselves, :func:`match_fields` runs the
 test on fields the caller holds and :func:`classes_from_leader` turns a leader array into dense
-class ids and sizes.
+class ids and sizes.  :class:`FoliationRegistry` keeps the classes across batches: the leaders'
+fields stay on the device and every batch of a stream is assigned against them.
 """
 from __future__ import annotations
 
@@ -171,3 +172,242 @@ def tag_known(ctx, pd_, classes: FoliationClasses, fields_or_programs, params: O
             same = (lead_fields == kf) | (torch.isnan(lead_fields) & torch.isnan(kf))
             hit[:, k] |= same.flatten(1).all(1).cpu().numpy()
     return {int(c): names[int(np.argmax(hit[c]))] for c in range(len(lead_rows)) if hit[c].any()}
+
+
+class FoliationRegistry:
+    """The foliation classes of a stream of batches (``pdeval_fol_registry_*``, DESIGN.md §14
+    "Registry"): the class leaders' gradient fields stay resident on ``ctx``'s device, a batch is
+    assigned against them in one pass, new leaders are appended and class ids -- dense int64 in
+    order of creation -- never change.  Assigning a list in any number of consecutive batches
+    gives the class ids :func:`classify` gives on the whole list.  The limit of the definition is
+    inherited: a function of one coordinate matches nothing, not even itself, so each such row
+    is a leader.  Calls are synchronous, on the context's stream; close the registry before its
+    context."""
+
+    def __init__(self, ctx, params: Optional[FolParams] = None, capacity_hint: int = 0):
+        import ctypes as C
+        from ._lib import _check
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        _check(ctx.h, self.lib.pdeval_fol_registry_create(ctx.h, C.byref(params) if params is not None else None,
+                                                          int(capacity_hint), C.byref(self.h)))
+        self.params = FolParams()
+        grid = np.zeros(8)
+        _check(ctx.h, self.lib.pdeval_fol_registry_info(self.h, C.byref(self.params), grid.ctypes.data, None))
+        self.grid = grid
+        self.mm = int(self.params.m) ** 2
+
+    # ---- lifetime
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.pdeval_fol_registry_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self.ctx.h:          # (a closed context has released the device already)
+                self.close()
+        except Exception:
+            pass
+
+    def _call(self, rc):
+        from ._lib import _check
+        _check(self.ctx.h, rc)
+
+    @staticmethod
+    def _keys(keys, n):
+        if keys is None:
+            return None
+        k = np.ascontiguousarray(keys, dtype=np.int64)
+        if k.shape != (n,):
+            raise ValueError(f'keys: expected {n} entries, got shape {k.shape}')
+        return k
+
+    # ---- assignment
+    def assign(self, d_ops, n_words: int, d_offsets, n: int, idx, keys=None) -> np.ndarray:
+        """int64 class ids of the candidates ``idx`` of the programs resident on the device
+        (``d_ops`` / ``d_offsets``: torch tensors or device addresses), -1 for a row with too few
+        finite points.  ``keys``: the caller's identifier of each row (kept for new leaders);
+        None = the running row number over all calls."""
+        import ctypes as C
+        import torch
+        dev = _device(self.ctx)
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        keys = self._keys(keys, len(idx))
+        d_list = torch.from_numpy(idx).to(dev)
+        torch.cuda.current_stream(dev).synchronize()   # (the call runs on the context's own stream)
+        cls = np.full(len(idx), -1, dtype=np.int64)
+        n_new = C.c_int64(0)
+        self._call(self.lib.pdeval_fol_registry_assign(
+            self.ctx.h, self.h, _ptr(d_ops) or None, n_words, _ptr(d_offsets) or None, n, d_list.data_ptr() or None,
+            len(idx), None if keys is None else keys.ctypes.data, cls.ctypes.data, C.byref(n_new)))
+        self.last_new = int(n_new.value)
+        return cls
+
+    def assign_fields(self, fields, n_finite=None, keys=None) -> np.ndarray:
+        """The same on fields the caller holds: a torch float64 tensor [rows, 2, m*m] on the
+        context's device (and optionally the int32 finite counts ``gradient_fields`` returns)."""
+        import ctypes as C
+        import torch
+        dev = _device(self.ctx)
+        if fields.dtype != torch.float64 or fields.dim() != 3 or tuple(fields.shape[1:]) != (2, self.mm) \
+                or fields.device != dev:
+            raise ValueError(f'fields: expected a float64 tensor [rows, 2, {self.mm}] on {dev}')
+        fields = fields.contiguous()
+        rows = int(fields.shape[0])
+        keys = self._keys(keys, rows)
+        nf = None
+        if n_finite is not None:
+            nf = n_finite.to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(nf.shape) != (rows,):
+                raise ValueError(f'n_finite: expected {rows} entries')
+        torch.cuda.current_stream(dev).synchronize()
+        cls = np.full(rows, -1, dtype=np.int64)
+        n_new = C.c_int64(0)
+        self._call(self.lib.pdeval_fol_registry_assign_fields(
+            self.ctx.h, self.h, fields.data_ptr() or None, None if nf is None else nf.data_ptr(), rows,
+            None if keys is None else keys.ctypes.data, cls.ctypes.data, C.byref(n_new)))
+        self.last_new = int(n_new.value)
+        return cls
+
+    # ---- what the registry holds
+    def _size(self):
+        import ctypes as C
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._call(self.lib.pdeval_fol_registry_size(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    @property
+    def n_classes(self) -> int:
+        return self._size()[0]
+
+    @property
+    def rows_seen(self) -> int:
+        return self._size()[1]
+
+    def _host(self):
+        L = self.n_classes
+        keys, sizes = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64)
+        self._call(self.lib.pdeval_fol_registry_leaders(self.h, None, keys.ctypes.data, sizes.ctypes.data))
+        return keys, sizes
+
+    @property
+    def sizes(self) -> np.ndarray:
+        return self._host()[1]
+
+    @property
+    def leader_keys(self) -> np.ndarray:
+        return self._host()[0]
+
+    @property
+    def stage_a_ms(self) -> float:
+        """Device time of Stage A's launch in the most recent assign call (0 if it ran none)."""
+        import ctypes as C
+        ms = C.c_double(0.0)
+        self._call(self.lib.pdeval_fol_registry_info(self.h, None, None, C.byref(ms)))
+        return float(ms.value)
+
+    def leader_fields(self):
+        """The leaders' fields, a torch float64 tensor [L, 2, m*m] on the context's device (a copy:
+        the store itself is chunk-major)."""
+        import torch
+        dev = _device(self.ctx)
+        L = self.n_classes
+        out = torch.empty((L, 2, self.mm), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        if L:
+            self._call(self.lib.pdeval_fol_registry_leaders(self.h, out.data_ptr(), None, None))
+        return out
+
+    def tags(self, pd_):
+        """{class_id: name} of the classes that re-parametrise one of ``pd_.known_solutions``, by
+        the two rules of :func:`tag_known` applied to the leaders' fields: the leader matches the
+        known solution under the Jacobian test, or its field equals the known one's at every
+        sample point."""
+        import torch
+        from . import problem_defs as P
+        if self.n_classes == 0:
+            return {}
+        dev = _device(self.ctx)
+        lead_fields = self.leader_fields()
+        names = list(pd_.known_solutions.values())
+        ops, off, _ = P.compile_strings(pd_, list(pd_.known_solutions))
+        k_ops = torch.from_numpy(np.ascontiguousarray(ops, dtype=np.int32)).to(dev)
+        k_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64)).to(dev)
+        known, _ = gradient_fields(self.ctx, k_ops, int(k_ops.numel()), k_off, len(names), None, self.params)
+        hit = match_fields(self.ctx, lead_fields, known, self.params)
+        for k in range(len(names)):
+            kf = known[k]
+            if bool(torch.isfinite(kf).any()):
+                same = (lead_fields == kf) | (torch.isnan(lead_fields) & torch.isnan(kf))
+                hit[:, k] |= same.flatten(1).all(1).cpu().numpy()
+        return {int(c): names[int(np.argmax(hit[c]))] for c in range(len(hit)) if hit[c].any()}
+
+    def merge(self, other: 'FoliationRegistry') -> np.ndarray:
+        """Takes ``other``'s classes into this registry: the sequential rule applied to
+        ``other``'s leaders, in their order, after this registry's own -- each joins the first
+        class of this registry it matches or becomes a new one (keeping its key) -- and
+        ``other``'s class sizes are added.  Returns the int64 map from ``other``'s class ids to
+        this registry's.  Members of ``other``'s classes follow their leader without being
+        tested again.  ``other`` is left as it is and may live on another context of the same
+        device, with the same m and grid."""
+        if int(other.params.m) != int(self.params.m) or not np.array_equal(other.grid, self.grid):
+            raise ValueError('merge: the registries differ in m or grid')
+        keys, sizes = other._host()
+        if len(keys) == 0:
+            return np.zeros(0, dtype=np.int64)
+        ids = self.assign_fields(other.leader_fields(), keys=keys)
+        extra = sizes - 1
+        self._call(self.lib.pdeval_fol_registry_add_sizes(self.h, ids.ctypes.data, extra.ctypes.data, len(ids)))
+        return ids
+
+    # ---- persistence
+    def save(self, path):
+        """One .npz: the leaders' fields, keys and sizes, m, tau, min_points and the context's 8
+        grid doubles."""
+        keys, sizes = self._host()
+        with open(path, 'wb') as f:
+            np.savez(f, fields=self.leader_fields().cpu().numpy(), keys=keys, sizes=sizes,
+                     m=np.int64(self.params.m), tau=np.float64(self.params.tau),
+                     min_points=np.int64(self.params.min_points), grid=self.grid)
+
+    @classmethod
+    def load(cls, ctx, path, params: Optional[FolParams] = None, capacity_hint: int = 0) -> 'FoliationRegistry':
+        """A registry on ``ctx`` holding the saved leaders as they were (no re-matching: ids are
+        preserved).  ``params`` (None: the file's) must agree with the file's ``m``, and the file's
+        grid with the context's: otherwise ValueError naming the field."""
+        import torch
+        with np.load(path) as d:
+            fields, keys, sizes = d['fields'], d['keys'], d['sizes']
+            m, tau, min_points, grid = int(d['m']), float(d['tau']), int(d['min_points']), d['grid']
+        if params is None:
+            params = default_fol_params()
+            params.m, params.tau, params.min_points = m, tau, min_points
+        if int(params.m) != m:
+            raise ValueError(f'{path}: m = {m} in the file, {int(params.m)} asked for')
+        reg = cls(ctx, params, max(capacity_hint, len(keys)))
+        try:
+            if not np.array_equal(reg.grid, grid):
+                raise ValueError(f'{path}: grid = {grid.tolist()} in the file, {reg.grid.tolist()} in the context')
+            if fields.shape != (len(keys), 2, m * m) or sizes.shape != keys.shape:
+                raise ValueError(f'{path}: fields {fields.shape} do not fit {len(keys)} classes at m = {m}')
+            dev = _device(ctx)
+            d_f = torch.from_numpy(np.ascontiguousarray(fields, dtype=np.float64)).to(dev)
+            keys = np.ascontiguousarray(keys, dtype=np.int64)
+            sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+            torch.cuda.current_stream(dev).synchronize()
+            reg._load(d_f, keys, sizes)
+        except Exception:
+            reg.close()
+            raise
+        return reg
+
+    def _load(self, d_fields, keys, sizes):
+        self._call(self.lib.pdeval_fol_registry_load(self.ctx.h, self.h, d_fields.data_ptr() or None, keys.ctypes.data,
+                                                     sizes.ctypes.data, len(keys)))
