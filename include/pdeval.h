@@ -317,13 +317,23 @@ int pdeval_comm_destroy(pdeval_ctx* ctx);
  * usable iff J and S are finite and S > 0, and bad iff |J| > tau S (no division).  A row matches
  * a probe iff n_used >= min_points and n_bad == 0.  The test does not involve the operator.  A
  * Kerr context returns PDEVAL_ERR_ARG (its equation is linear: re-parametrisation is no
- * symmetry there).                                                                           */
+ * symmetry there).
+ * The axis rule (flags & PDEVAL_FOL_AXIS; off by default): between two functions of rho alone
+ * both products vanish, S == 0 and no point is usable, so without the rule rho**2 and rho**4 are
+ * separate classes and rho**2 does not match itself; likewise for functions of z alone.  With
+ * the rule a point with S == 0 is usable, and never bad, when a, b, c, d are all finite and
+ * either b == 0, d == 0, a != 0, c != 0 (both gradients along rho: the cylinders rho = const) or
+ * a == 0, c == 0, b != 0, d != 0 (both along z: the planes z = const).  The test is on the
+ * operands, not the products; such a point adds 1 to n_used and 0 to qmax.  A zero gradient
+ * still matches nothing.  Every entry point below takes the flag from the parameters it is given
+ * (a registry: from those it was created with); with the bit clear every result is what it was. */
 typedef struct pdeval_fol_params {
     double tau;          /* a usable point is bad iff |J| > tau * S (1e-7, the grid's tau_grid) */
     int32_t m;           /* sample grid m x m, 4 <= m <= 64 (16)                                 */
     int32_t min_points;  /* usable points a match needs (16)                                     */
-    int32_t reserved;
+    int32_t flags;       /* PDEVAL_FOL_* bits (0); other bits are ignored                        */
 } pdeval_fol_params;
+#define PDEVAL_FOL_AXIS 1   /* functions of one coordinate form one class per axis (above)       */
 #define PDEVAL_FOL_MAX_PROBES 32
 int pdeval_default_fol_params(pdeval_fol_params* out);
 /* Device pointers, asynchronous on `stream` (NULL = the context's).  d_mask[row]: bit k set iff
@@ -346,6 +356,13 @@ int pdeval_jacobian_match(pdeval_ctx* ctx, const double* d_rows_field, int64_t n
 int pdeval_gradient_fields(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
                            int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
                            double* d_field, int32_t* d_n_finite, void* stream);
+/* The kind of each row of d_fields ([n_rows][2][m^2], device): d_kind[row] (device, uint8) = 1
+ * (rho-axis) iff u_z == 0 at every finite point of the row -- u_rho and u_z both finite -- and
+ * u_rho != 0 at >= min_points of them; 2 (z-axis) the mirror image; 0 otherwise.  These are the
+ * rows the axis rule gathers into one class per axis.  Independent of params->flags.
+ * Asynchronous on `stream` (NULL = the context's).                                             */
+int pdeval_field_kinds(pdeval_ctx* ctx, const double* d_fields, int64_t n_rows, const pdeval_fol_params* params,
+                       uint8_t* d_kind, void* stream);
 /* The classes of the list, synchronous: computes the fields on the device (n_list x 2 m^2 x 8
  * bytes, allocated for the call; PDEVAL_ERR_ALLOC if that fails), leaves rows with n_finite <
  * min_points unclassified (leader -1) and groups the others in rounds: each round matches the
@@ -367,9 +384,9 @@ int pdeval_foliation_classes(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_wo
  * pdeval_foliation_classes; their leaders get the ids L, L+1, ... in list order and their fields
  * are appended.  Class ids are dense, in order of creation, and never change; a row with fewer
  * than min_points finite points gets -1.  Assigning a list in any number of consecutive batches
- * gives the classes pdeval_foliation_classes gives on the whole list.  The limit of the
- * definition is inherited: a function of one coordinate matches nothing, not even itself, so
- * every such row is a leader.
+ * gives the classes pdeval_foliation_classes gives on the whole list.  Without PDEVAL_FOL_AXIS
+ * in the registry's parameters a function of one coordinate matches nothing, not even itself,
+ * so every such row is a leader; with it they form one class per axis.
  * A registry is bound to the force-free context and the parameters it was created with; every
  * call that runs on the device takes that context and returns PDEVAL_ERR_ARG for another one.
  * The calls are synchronous, on the context's stream.  The leader store grows by doubling
@@ -404,9 +421,11 @@ int pdeval_fol_registry_leaders(pdeval_fol_registry* reg, double* d_fields, int6
  * otherwise PDEVAL_ERR_ARG.  The count of rows seen restarts at the sum of the sizes.          */
 int pdeval_fol_registry_load(pdeval_ctx* ctx, pdeval_fol_registry* reg, const double* d_fields,
                              const int64_t* leader_keys, const int64_t* sizes, int64_t n_classes);
-/* Any argument may be NULL.  params: the registry's; grid: the 8 grid doubles of its context
- * {x_lo, x_hi, nx, y_lo, y_hi, ny, x_phase, y_phase}; *stage_a_ms: the device time of Stage A's
- * launch in the most recent assign call (HIP events; 0 if it launched none).                   */
+/* kinds (host, n_classes): pdeval_field_kinds of the leaders' fields, read from the store.    */
+int pdeval_fol_registry_kinds(pdeval_fol_registry* reg, uint8_t* kinds);
+/* Any argument may be NULL.  params: the registry's, its flags among them; grid: the 8 grid
+ * doubles of its context {x_lo, x_hi, nx, y_lo, y_hi, ny, x_phase, y_phase}; *stage_a_ms: the
+ * device time of Stage A's launch in the most recent assign call (HIP events; 0 if none ran).  */
 int pdeval_fol_registry_info(pdeval_fol_registry* reg, pdeval_fol_params* params, double* grid, double* stage_a_ms);
 /* count[k] rows more in class class_id[k] (host arrays of n), rows that were classified
  * elsewhere: how the sizes of a merged registry are carried over.                              */

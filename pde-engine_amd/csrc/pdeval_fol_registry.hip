@@ -26,7 +26,8 @@ namespace pd {
 // only its first chunk does and the later ones are re-read per surviving pair.  Counts are
 // ballots into wave-uniform counters; a row is finished at its first match and a block when
 // its four rows are.  The only indices read are row < n_rows and leader < L, both loop bounds.
-template <bool REG>
+// AXIS: the chunk test with the axis rule (PDEVAL_FOL_AXIS); AXIS = false is the kernel as it was.
+template <bool REG, bool AXIS>
 __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
     constexpr int T = kFolAssignTile, NR = REG ? kFolRegChunks : 1;
     constexpr int kPf = T * 2 * kFolChunk / 2 / 256;   // double2 per thread and tile
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
             for (int k = 0; k < tn; ++k) {
                 const double* q0 = tile + k * 2 * kFolChunk;
                 FolCount n{0, 0};
-                fol_chunk_test(fa[0], fb[0], q0[lane], q0[kFolChunk + lane], lane < mm, a.tau, n);
+                fol_chunk_test<AXIS>(fa[0], fb[0], q0[lane], q0[kFolChunk + lane], lane < mm, a.tau, n);
                 if (n.nb) continue;
                 const int64_t l = t0 + k;
                 if constexpr (REG) {
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
                     for (int c = 1; c < NR; ++c)
                         if (c < a.n_chunk && !n.nb) {
                             const double* q = a.store + fol_store_at(a.cap, c, l);
-                            fol_chunk_test(fa[c], fb[c], q[lane], q[kFolChunk + lane], c * kFolChunk + lane < mm,
+                            fol_chunk_test<AXIS>(fa[c], fb[c], q[lane], q[kFolChunk + lane], c * kFolChunk + lane < mm,
                                            a.tau, n);
                         }
                 } else {
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
                         const double* q = a.store + fol_store_at(a.cap, c, l);
                         const int p = c * kFolChunk + lane;
                         const int pc = p < mm ? p : mm - 1;
-                        fol_chunk_test(ra[pc], ra[mm + pc], q[lane], q[kFolChunk + lane], p < mm, a.tau, n);
+                        fol_chunk_test<AXIS>(ra[pc], ra[mm + pc], q[lane], q[kFolChunk + lane], p < mm, a.tau, n);
                     }
                 }
                 if (n.nu >= a.min_points && n.nb == 0) {
@@ -107,8 +108,11 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
 
 void launch_fol_assign(const FolAssignArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.n_rows + 3) / 4)), block(256);
-    if (a.n_chunk <= kFolRegChunks) hipLaunchKernelGGL(fol_assign_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(fol_assign_kernel<false>, grid, block, 0, s, a);
+    const bool reg = a.n_chunk <= kFolRegChunks, axis = (a.flags & PDEVAL_FOL_AXIS) != 0;
+    if (reg && !axis) hipLaunchKernelGGL((fol_assign_kernel<true, false>), grid, block, 0, s, a);
+    else if (!reg && !axis) hipLaunchKernelGGL((fol_assign_kernel<false, false>), grid, block, 0, s, a);
+    else if (reg) hipLaunchKernelGGL((fol_assign_kernel<true, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((fol_assign_kernel<false, true>), grid, block, 0, s, a);
 }
 
 // One wave per (leader, chunk) of the call.  to_store: leader k's field, fields[idx[k]] (or
@@ -311,6 +315,7 @@ int reg_assign(pdeval_fol_registry* r, const double* d_fields, const int32_t* d_
         a.tau = r->prm.tau;
         a.min_points = r->prm.min_points;
         a.first = r->d_first;
+        a.flags = (uint32_t)r->prm.flags;
         (void)hipEventRecord(r->e0, s);
         launch_fol_assign(a, s);
         if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_assign_kernel", e);
@@ -490,6 +495,36 @@ extern "C" int pdeval_fol_registry_leaders(pdeval_fol_registry* r, double* d_fie
     launch_fol_move(m, r->v.stream);
     if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
     if ((e = hipStreamSynchronize(r->v.stream)) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
+    return PDEVAL_OK;
+}
+
+extern "C" int pdeval_fol_registry_kinds(pdeval_fol_registry* r, uint8_t* kinds) {
+    if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_kinds: null registry");
+    pdeval_ctx* c = r->ctx;
+    const int64_t L = r->book.n_classes();
+    if (L == 0) return PDEVAL_OK;
+    if (!kinds) return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry_kinds: bad argument");
+    hipError_t e = hipSetDevice(r->v.device);
+    if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
+    uint8_t* d_kind = nullptr;
+    if (hipMalloc((void**)&d_kind, (size_t)L) != hipSuccess) {
+        (void)hipGetLastError();
+        return fol_fail(c, PDEVAL_ERR_ALLOC, "pdeval_fol_registry_kinds: cannot allocate the kinds");
+    }
+    FolKindArgs a{};
+    a.fields = r->d_store;   // the leaders where they are: chunk-major (fol_store_at)
+    a.n_rows = L;
+    a.cap = r->cap;
+    a.mm = r->mm;
+    a.n_chunk = r->n_chunk;
+    a.min_points = r->prm.min_points;
+    a.kind = d_kind;
+    launch_fol_kind(a, r->v.stream);
+    if ((e = hipGetLastError()) == hipSuccess)
+        e = hipMemcpyAsync(kinds, d_kind, (size_t)L, hipMemcpyDeviceToHost, r->v.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->v.stream);
+    (void)hipFree(d_kind);
+    if (e != hipSuccess) return fol_hip_fail(c, "fol_kind_kernel", e);
     return PDEVAL_OK;
 }
 

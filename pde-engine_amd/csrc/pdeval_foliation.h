@@ -28,10 +28,18 @@ namespace pd {
 // iff |J| > tau S.  The two products are rounded separately (no FMA), so J is antisymmetric
 // under the exchange of row and probe bit for bit and the host restatement computes the same
 // doubles.
+// AXIS (PDEVAL_FOL_AXIS): a point the test above leaves unusable is usable, and never bad, when
+// all four operands are finite and both gradients lie along the same coordinate axis -- b == 0,
+// d == 0, a != 0, c != 0 (functions of rho alone: the cylinders rho = const) or the mirror image
+// (functions of z alone).  The test is on the operands, not on the products: there both products
+// are exact zeros, J = S = 0, and a product that merely underflowed does not count.  A zero
+// gradient of either side still says nothing.  Symmetric under the exchange of row and probe.
+// AXIS = false is the test as it was; callers that name no AXIS get it.
 struct FolPoint {
     double J, S;
     bool used, bad;
 };
+template <bool AXIS = false>
 PD_HD FolPoint fol_point_test(double a, double b, double c, double d, double tau) {
 #pragma clang fp contract(off)
     const double ad = a * d, bc = b * c;
@@ -40,10 +48,21 @@ PD_HD FolPoint fol_point_test(double a, double b, double c, double d, double tau
     r.S = fabs(ad) + fabs(bc);
     r.used = finite_(r.J) && finite_(r.S) && r.S > 0.0;
     r.bad = r.used && fabs(r.J) > tau * r.S;
+    if constexpr (AXIS) {
+        const bool fin = finite_(a) && finite_(b) && finite_(c) && finite_(d);
+        const bool along_rho = b == 0.0 && d == 0.0 && a != 0.0 && c != 0.0;
+        const bool along_z = a == 0.0 && c == 0.0 && b != 0.0 && d != 0.0;
+        r.used = r.used || (fin && (along_rho || along_z));
+    }
     return r;
 }
-// the diagnostic q = |J| / S of a usable point (IEEE division)
-PD_HD double fol_q(const FolPoint& r) { return fabs(r.J) / r.S; }
+// the diagnostic q = |J| / S of a usable point (IEEE division); AXIS: 0 at a point usable by the
+// axis rule (S == 0), never 0 / 0
+template <bool AXIS = false>
+PD_HD double fol_q(const FolPoint& r) {
+    if constexpr (AXIS) return r.S > 0.0 ? fabs(r.J) / r.S : 0.0;
+    else return fabs(r.J) / r.S;
+}
 
 // ---------------------------------------------------------------- the gradient field (host + device)
 // The field of a program: (u_rho, u_z) of its order-1 jet at the m x m sample points of the
@@ -172,11 +191,36 @@ PD_HD int64_t fol_store_at(int64_t cap, int chunk, int64_t leader) {
 struct FolCount {
     int nu, nb;
 };
+template <bool AXIS = false>
 __device__ __forceinline__ void fol_chunk_test(double a, double b, double c, double d, bool active, double tau,
                                                FolCount& n) {
-    const FolPoint t = fol_point_test(a, b, c, d, tau);
+    const FolPoint t = fol_point_test<AXIS>(a, b, c, d, tau);
     n.nu += count_lanes(active && t.used);
     n.nb += count_lanes(active && t.bad);
+}
+
+// ---------------------------------------------------------------- the kind of a field (host + device)
+// Whether a field is that of a function of one coordinate (fol_kind_kernel): over its finite
+// points -- u_rho and u_z both finite -- kind 1 (rho-axis) iff u_z == 0 at every one and u_rho != 0
+// at >= min_points of them, kind 2 (z-axis) the mirror image, 0 otherwise.  The two exclude
+// each other.  This lane's point is added to the row's wave-uniform counts by a ballot each (one
+// lane under PD_HOST_SIM).
+struct FolKindCount {
+    int a_nz, b_nz;   // finite points with u_rho != 0, with u_z != 0
+    int a_ax, b_ax;   // finite points with u_z == 0 and u_rho != 0, with u_rho == 0 and u_z != 0
+};
+__device__ __forceinline__ void fol_kind_chunk(double a, double b, bool active, FolKindCount& n) {
+    const bool fin = active && finite_(a) && finite_(b);
+    const bool anz = fin && a != 0.0, bnz = fin && b != 0.0;
+    n.a_nz += count_lanes(anz);
+    n.b_nz += count_lanes(bnz);
+    n.a_ax += count_lanes(anz && !bnz);
+    n.b_ax += count_lanes(bnz && !anz);
+}
+PD_HD int fol_kind_of(const FolKindCount& n, int min_points) {
+    if (n.b_nz == 0 && n.a_ax >= min_points) return 1;
+    if (n.a_nz == 0 && n.b_ax >= min_points) return 2;
+    return 0;
 }
 
 #ifndef PD_HOST_SIM
@@ -196,6 +240,7 @@ struct FolMatchArgs {
     // probes): row r's field is rows[idx[r]], probe k's is probes[pidx[k]]; NULL = r, k
     const int64_t* idx;
     const int64_t* pidx;
+    uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernel's AXIS instantiation
 };
 void launch_fol_match(const FolMatchArgs& a, hipStream_t s);
 
@@ -226,6 +271,7 @@ struct FolAssignArgs {
     double tau;
     int min_points;
     int64_t* first;            // n_rows
+    uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernel's AXIS instantiations
 };
 void launch_fol_assign(const FolAssignArgs& a, hipStream_t s);
 
@@ -244,6 +290,18 @@ struct FolMoveArgs {
 void launch_fol_move(const FolMoveArgs& a, hipStream_t s);
 // n_finite[row] = the points of the row with a finite u_rho (fields the caller holds)
 void launch_fol_nfinite(const double* fields, int64_t n_rows, int mm, int32_t* n_finite, hipStream_t s);
+
+// kind[row] of fol_kind_of: rows of [n_rows][2][mm] fields (cap == 0), or the leaders 0 .. n_rows-1
+// of a chunk-major store of capacity cap (fol_store_at).  One wave per row.
+struct FolKindArgs {
+    const double* fields;
+    int64_t n_rows;
+    int64_t cap;
+    int mm, n_chunk;
+    int min_points;
+    uint8_t* kind;             // n_rows
+};
+void launch_fol_kind(const FolKindArgs& a, hipStream_t s);
 
 // what the entry points (pdeval_foliation.hip, pdeval_fol_registry.hip) need of a context (pdeval.hip)
 struct FolCtx {

@@ -22,6 +22,8 @@ namespace pd {
 // LDS holds -- against 4 MiB of L2 per XCD); every wave reads them in the same order, coalesced.
 // The row's own field (4 KiB at m = 16) is re-read once per probe and stays in the CU's L1.
 // Without the diagnostics a probe is left at its first bad point: the mask is decided.
+// AXIS: the point test with the axis rule (PDEVAL_FOL_AXIS); AXIS = false is the kernel as it was.
+template <bool AXIS>
 __global__ __launch_bounds__(256) void fol_match_kernel(FolMatchArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -40,10 +42,10 @@ __global__ __launch_bounds__(256) void fol_match_kernel(FolMatchArgs a) {
             const int p = p0 + lane;
             const bool active = p < mm;
             const int pc = active ? p : mm - 1;   // (lanes past m^2 re-read the last point, uncounted)
-            const FolPoint t = fol_point_test(ra[pc], ra[mm + pc], pa[pc], pa[mm + pc], a.tau);
+            const FolPoint t = fol_point_test<AXIS>(ra[pc], ra[mm + pc], pa[pc], pa[mm + pc], a.tau);
             nu += count_lanes(active && t.used);
             nb += count_lanes(active && t.bad);
-            if (a.qmax && active && t.used) q = fmax(q, fol_q(t));
+            if (a.qmax && active && t.used) q = fmax(q, fol_q<AXIS>(t));
             if (!diag && nb) break;
         }
         if (nu >= a.min_points && nb == 0) mask |= 1u << k;
@@ -57,7 +59,43 @@ __global__ __launch_bounds__(256) void fol_match_kernel(FolMatchArgs a) {
 }
 
 void launch_fol_match(const FolMatchArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(fol_match_kernel, dim3((unsigned)((a.n_rows + 3) / 4)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((a.n_rows + 3) / 4)), block(256);
+    if (a.flags & PDEVAL_FOL_AXIS) hipLaunchKernelGGL(fol_match_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(fol_match_kernel<false>, grid, block, 0, s, a);
+}
+
+// One wave per row, four rows per block; lanes are sample points.  The row's finite points are
+// sorted into the four counts of fol_kind_chunk with a ballot each (wave-uniform counters in
+// SGPRs) and lane 0 stores the row's kind as one byte.  The row is read from [n_rows][2][mm]
+// fields, or (cap > 0) from leader `row` of a chunk-major store, whose points past m^2 hold NaN.
+// The only index read is row < n_rows.
+__global__ __launch_bounds__(256) void fol_kind_kernel(FolKindArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (row >= a.n_rows) return;
+    const int mm = a.mm;
+    FolKindCount n{0, 0, 0, 0};
+    for (int c = 0; c < a.n_chunk; ++c) {
+        const int p = c * kFolChunk + lane;
+        const bool active = p < mm;
+        double u, v;
+        if (a.cap > 0) {
+            const double* q = a.fields + fol_store_at(a.cap, c, row);
+            u = q[lane];
+            v = q[kFolChunk + lane];
+        } else {
+            const double* ra = a.fields + row * 2 * (int64_t)mm;
+            const int pc = active ? p : mm - 1;   // (lanes past m^2 re-read the last point, uncounted)
+            u = ra[pc];
+            v = ra[mm + pc];
+        }
+        fol_kind_chunk(u, v, active, n);
+    }
+    if (lane == 0) a.kind[row] = (uint8_t)fol_kind_of(n, a.min_points);
+}
+
+void launch_fol_kind(const FolKindArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(fol_kind_kernel, dim3((unsigned)((a.n_rows + 3) / 4)), dim3(256), 0, s, a);
 }
 
 // One wave per (list row, 64-point chunk), four waves per block; lanes are sample points.  The
@@ -109,7 +147,7 @@ extern "C" int pdeval_default_fol_params(pdeval_fol_params* p) {
     p->tau = 1e-7;   // the grid stage's tau_grid (pdeval_default_params)
     p->m = 16;
     p->min_points = 16;
-    p->reserved = 0;
+    p->flags = 0;
     return PDEVAL_OK;
 }
 
@@ -148,6 +186,7 @@ extern "C" int pdeval_jacobian_match(pdeval_ctx* c, const double* d_rows_field, 
     a.mask = d_mask;
     a.n_used = d_n_used;
     a.qmax = d_qmax;
+    a.flags = (uint32_t)prm.flags;
     launch_fol_match(a, stream ? (hipStream_t)stream : v.stream);
     e = hipGetLastError();
     if (e != hipSuccess) return fol_fail(c, PDEVAL_ERR_HIP, (std::string("fol_match_kernel: ") + hipGetErrorString(e)).c_str());
@@ -229,6 +268,7 @@ int fol_rounds(pdeval_ctx* c, const double* d_field, int mm, const pdeval_fol_pa
         a.mask = d_mask;
         a.idx = d_idx;
         a.pidx = d_idx;   // the round's probes: its first np rows
+        a.flags = (uint32_t)prm.flags;
         launch_fol_match(a, s);
         if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_match_kernel", e);
         if ((e = hipMemcpyAsync(mask.data(), d_mask, (size_t)nu * sizeof(uint32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
@@ -257,6 +297,30 @@ extern "C" int pdeval_gradient_fields(pdeval_ctx* c, const int32_t* d_ops, int64
     if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
     return fol_fields_launch(c, v, prm, d_ops, n_words, d_offsets, n, d_list, n_list, d_field, d_n_finite,
                              stream ? (hipStream_t)stream : v.stream);
+}
+
+extern "C" int pdeval_field_kinds(pdeval_ctx* c, const double* d_fields, int64_t n_rows,
+                                  const pdeval_fol_params* params, uint8_t* d_kind, void* stream) {
+    FolCtx v;
+    pdeval_fol_params prm;
+    const int rc = fol_check(c, "pdeval_field_kinds", nullptr, 0, nullptr, 0, 0, params, &v, &prm);
+    if (rc != PDEVAL_OK) return rc;
+    if (n_rows < 0 || n_rows > PDEVAL_MAX_BATCH || (n_rows > 0 && (!d_fields || !d_kind)))
+        return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_field_kinds: bad argument");
+    if (n_rows == 0) return PDEVAL_OK;
+    hipError_t e = hipSetDevice(v.device);
+    if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
+    FolKindArgs a{};
+    a.fields = d_fields;
+    a.n_rows = n_rows;
+    a.cap = 0;
+    a.mm = prm.m * prm.m;
+    a.n_chunk = (a.mm + kFolChunk - 1) / kFolChunk;
+    a.min_points = prm.min_points;
+    a.kind = d_kind;
+    launch_fol_kind(a, stream ? (hipStream_t)stream : v.stream);
+    if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_kind_kernel", e);
+    return PDEVAL_OK;
 }
 
 extern "C" int pdeval_foliation_classes(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words,

@@ -32,6 +32,7 @@ EXPORTS = (
     'pdeval_fol_registry_create', 'pdeval_fol_registry_destroy', 'pdeval_fol_registry_assign',
     'pdeval_fol_registry_assign_fields', 'pdeval_fol_registry_size', 'pdeval_fol_registry_leaders',
     'pdeval_fol_registry_load', 'pdeval_fol_registry_info', 'pdeval_fol_registry_add_sizes',
+    'pdeval_field_kinds', 'pdeval_fol_registry_kinds',
 )
 MAX_BATCH = 1 << 30          # PDEVAL_MAX_BATCH
 UNIQUE_ID_BYTES = 128
@@ -41,6 +42,7 @@ LIST_NAMES = ('defer_stack3', 'complex', 'defer_stack8', 'tier2', 'tier2_stack3'
               'grid_slow_complex')
 N_PASSES = 12
 FOL_MAX_PROBES = 32          # PDEVAL_FOL_MAX_PROBES
+FOL_AXIS = 1                 # PDEVAL_FOL_AXIS: functions of one coordinate form one class per axis
 
 
 class Params(C.Structure):
@@ -70,8 +72,9 @@ class KerrConstants(C.Structure):
 
 
 class FolParams(C.Structure):
-    """pdeval_fol_params (include/pdeval.h): the Jacobian test on an m x m sample grid."""
-    _fields_ = [('tau', C.c_double), ('m', C.c_int32), ('min_points', C.c_int32), ('reserved', C.c_int32)]
+    """pdeval_fol_params (include/pdeval.h): the Jacobian test on an m x m sample grid; ``flags``
+    holds the PDEVAL_FOL_* bits (``FOL_AXIS``)."""
+    _fields_ = [('tau', C.c_double), ('m', C.c_int32), ('min_points', C.c_int32), ('flags', C.c_int32)]
 
 
 class PdevalError(RuntimeError):
@@ -141,6 +144,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_fol_registry_load.argtypes = [vp, vp, vp, vp, vp, i64]
     lib.pdeval_fol_registry_info.argtypes = [vp, C.POINTER(FolParams), vp, C.POINTER(dbl)]
     lib.pdeval_fol_registry_add_sizes.argtypes = [vp, vp, vp, i64]
+    lib.pdeval_field_kinds.argtypes = [vp, vp, i64, C.POINTER(FolParams), vp, vp]
+    lib.pdeval_fol_registry_kinds.argtypes = [vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -155,6 +160,16 @@ def default_params(problem_id: int) -> Params:
 def default_fol_params() -> FolParams:
     p = FolParams()
     _check(None, load().pdeval_default_fol_params(C.byref(p)))
+    return p
+
+
+def fol_params(params: Optional[FolParams] = None, axis: Optional[bool] = None) -> FolParams:
+    """A copy of ``params`` (None: the defaults); ``axis`` True / False sets / clears ``FOL_AXIS``
+    in its flags, None leaves them."""
+    src = params if params is not None else default_fol_params()
+    p = FolParams(src.tau, src.m, src.min_points, src.flags)
+    if axis is not None:
+        p.flags = (int(p.flags) | FOL_AXIS) if axis else (int(p.flags) & ~FOL_AXIS)
     return p
 
 
@@ -334,6 +349,14 @@ class Context:
         prm = params if params is not None else default_fol_params()
         _check(self.h, self.lib.pdeval_gradient_fields(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
                                                        C.byref(prm), d_field, d_n_finite or None, stream or None))
+
+    def field_kinds(self, d_fields: int, n_rows: int, d_kind: int, params: Optional[FolParams] = None,
+                    stream: int = 0):
+        """Device pointers, asynchronous: d_kind[row] (uint8) = 1 for the field of a function of rho
+        alone, 2 of z alone, 0 otherwise (pdeval_field_kinds); d_fields [n_rows, 2, m*m]."""
+        prm = params if params is not None else default_fol_params()
+        _check(self.h, self.lib.pdeval_field_kinds(self.h, d_fields or None, n_rows, C.byref(prm), d_kind or None,
+                                                   stream or None))
 
     def foliation_classes(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int,
                           params: Optional[FolParams] = None):

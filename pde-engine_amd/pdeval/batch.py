@@ -824,18 +824,22 @@ class BatchValidator:
         ops, off, notes = compile_strings(self.pd, list(strings), stats=stats)
         return self._verdicts(ops, off, notes, list(strings), symbolic, symbolic_timeout)
 
-    def foliation_classes(self, strings: Sequence[str], params=None):
+    def foliation_classes(self, strings: Sequence[str], params=None, axis=None):
         """The foliation classes of the accepted candidates among ``strings`` (force-free; DESIGN.md
         §14): compiles and validates them, uploads the programs once and classifies the rows the
         device accepted (``CLS_ACCEPT``, before any host step) with ``pdeval.foliation.classify``.
         Returns ``(classes, accepted, tags)``: the ``FoliationClasses`` over the accepted rows
         (``leader`` holds indices into ``strings``), the accepted indices, and ``{class_id: name}``
-        of the classes that re-parametrise a known solution (``pdeval.foliation.tag_known``)."""
+        of the classes that re-parametrise a known solution (``pdeval.foliation.tag_known``).
+        The axis rule (functions of one coordinate form one class per axis) is taken from
+        ``params.flags`` (``FOL_AXIS``); ``axis=True`` / ``False`` sets / clears it."""
         if self.pd.problem_id != PROBLEM_FORCE_FREE:
             raise ValueError('foliation classes are a force-free notion (the Kerr equation is linear: '
                              'u -> f(u) is no symmetry of it)')
         import torch
         from . import foliation as F
+        if axis is not None:
+            params = F.fol_params(params, axis)
         from .native import compile_strings
         ops, off, _ = compile_strings(self.pd, list(strings))
         accepted = np.flatnonzero(np.asarray(self.run(ops, off)['status']) == CLS_ACCEPT).astype(np.int64)
@@ -848,19 +852,25 @@ class BatchValidator:
             tags = F.tag_known(self.ctx, self.pd, classes, (d_ops, n_words, d_off, n), params)
         return classes, accepted, tags
 
-    def foliation_registry(self, params=None, capacity_hint: int = 0):
+    def foliation_registry(self, params=None, capacity_hint: int = 0, axis=None):
         """A ``pdeval.foliation.FoliationRegistry`` on this validator's context (force-free): the
-        streaming caller holds it next to the validator and passes it to ``assign_foliation``."""
+        streaming caller holds it next to the validator and passes it to ``assign_foliation``, which
+        follows the registry's parameters.  The axis rule is taken from ``params.flags``
+        (``FOL_AXIS``); ``axis=True`` / ``False`` sets / clears it."""
         if self.pd.problem_id != PROBLEM_FORCE_FREE:
             raise ValueError('foliation classes are a force-free notion (the Kerr equation is linear: '
                              'u -> f(u) is no symmetry of it)')
+        if axis is not None:
+            from .foliation import fol_params
+            params = fol_params(params, axis)
         with self._lock:
             return self.ctx.fol_registry(params, capacity_hint)
 
     def assign_foliation(self, registry, strings: Sequence[str], keys=None):
         """One batch of a stream into ``registry`` (``foliation_registry``): compiles and validates
         ``strings``, uploads the programs once and assigns the rows the device accepted
-        (``CLS_ACCEPT``, before any host step).  ``keys`` (one per string, optional): the caller's
+        (``CLS_ACCEPT``, before any host step), under the parameters the registry was created with
+        (its ``FOL_AXIS`` flag among them).  ``keys`` (one per string, optional): the caller's
         identifiers; the accepted rows' keys go to the registry.  Returns ``(class_id_of_accepted,
         accepted_idx)``: the registry's class ids of the accepted rows and their indices into
         ``strings``."""

@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import FOL_MAX_PROBES, FolParams, default_fol_params
+from ._lib import FOL_AXIS, FOL_MAX_PROBES, FolParams, default_fol_params, fol_params  # noqa: F401
 
 
 @dataclass
@@ -82,6 +82,29 @@ def match_fields(ctx, rows, probes, params: Optional[FolParams] = None, diagnost
     return (hit, used, qmax) if diagnostics else hit
 
 
+def field_kinds(ctx, fields, params: Optional[FolParams] = None) -> np.ndarray:
+    """uint8[n_rows]: 1 for a row whose field is that of a function of ``rho`` alone (``u_z == 0`` at
+    every finite point, ``u_rho != 0`` at ``min_points`` of them or more), 2 for a function of ``z``
+    alone, 0 otherwise (``pdeval_field_kinds``).  ``fields``: a torch float64 tensor [rows, 2, m*m]
+    on ``ctx``'s device.  Does not depend on ``params.flags``."""
+    import torch
+    prm = params if params is not None else default_fol_params()
+    dev = _device(ctx)
+    mm = int(prm.m) ** 2
+    if fields.dtype != torch.float64 or fields.dim() != 3 or tuple(fields.shape[1:]) != (2, mm) or fields.device != dev:
+        raise ValueError(f'fields: expected a float64 tensor [rows, 2, {mm}] on {dev}')
+    fields = fields.contiguous()
+    rows = int(fields.shape[0])
+    st = torch.cuda.Stream(dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(st):
+        kind = torch.zeros(rows, dtype=torch.uint8, device=dev)
+        if rows:
+            ctx.field_kinds(fields.data_ptr(), rows, kind.data_ptr(), prm, st.cuda_stream)
+    st.synchronize()
+    return kind.cpu().numpy()
+
+
 def _ptr(t) -> int:
     """The device address of a torch tensor, or the integer address itself."""
     return int(t.data_ptr()) if hasattr(t, 'data_ptr') else int(t)
@@ -139,7 +162,8 @@ def tag_known(ctx, pd_, classes: FoliationClasses, fields_or_programs, params: O
     ``fields_or_programs`` supplies the leaders' fields: either the torch float64 [n_rows, 2, m*m]
     fields of the classified rows (row order of ``classes``), or the tuple ``(d_ops, n_words,
     d_offsets, n)`` of the resident programs ``classes.leader`` indexes, whose leader fields are
-    then computed here.  A leader whose field equals a known solution's at every sample point (the
+    then computed here.  With ``FOL_AXIS`` in ``params.flags`` the match includes the axis rule, and
+    the Vertical field (``rho**2``) is found by it.  A leader whose field equals a known solution's at every sample point (the
     same finite points, the same values) matches it too: equal gradients are the same ``u`` up to
     a constant, and the Jacobian test alone cannot say so for a function of one coordinate, which
     has no usable point against itself (``rho**2``, the Vertical field).  A class
@@ -179,9 +203,9 @@ class FoliationRegistry:
     "Registry"): the class leaders' gradient fields stay resident on ``ctx``'s device, a batch is
     assigned against them in one pass, new leaders are appended and class ids -- dense int64 in
     order of creation -- never change.  Assigning a list in any number of consecutive batches
-    gives the class ids :func:`classify` gives on the whole list.  The limit of the definition is
-    inherited: a function of one coordinate matches nothing, not even itself, so each such row
-    is a leader.  Calls are synchronous, on the context's stream; close the registry before its
+    gives the class ids :func:`classify` gives on the whole list.  Without ``FOL_AXIS`` in the
+    flags of ``params`` a function of one coordinate matches nothing, not even itself, so each such
+    row is a leader; with it they form one class per axis.  Calls are synchronous, on the context's stream; close the registry before its
     context."""
 
     def __init__(self, ctx, params: Optional[FolParams] = None, capacity_hint: int = 0):
@@ -313,6 +337,14 @@ class FoliationRegistry:
         self._call(self.lib.pdeval_fol_registry_info(self.h, None, None, C.byref(ms)))
         return float(ms.value)
 
+    def kinds(self) -> np.ndarray:
+        """uint8[n_classes]: :func:`field_kinds` of the leaders (``pdeval_fol_registry_kinds``): 1 for
+        a leader that is a function of ``rho`` alone, 2 of ``z`` alone, 0 otherwise."""
+        kinds = np.zeros(self.n_classes, dtype=np.uint8)
+        if kinds.size:
+            self._call(self.lib.pdeval_fol_registry_kinds(self.h, kinds.ctypes.data))
+        return kinds
+
     def leader_fields(self):
         """The leaders' fields, a torch float64 tensor [L, 2, m*m] on the context's device (a copy:
         the store itself is chunk-major)."""
@@ -356,9 +388,12 @@ class FoliationRegistry:
         ``other``'s class sizes are added.  Returns the int64 map from ``other``'s class ids to
         this registry's.  Members of ``other``'s classes follow their leader without being
         tested again.  ``other`` is left as it is and may live on another context of the same
-        device, with the same m and grid."""
+        device, with the same m, grid and flags."""
         if int(other.params.m) != int(self.params.m) or not np.array_equal(other.grid, self.grid):
             raise ValueError('merge: the registries differ in m or grid')
+        if (int(other.params.flags) ^ int(self.params.flags)) & FOL_AXIS:
+            raise ValueError(f'merge: the registries differ in flags ({int(self.params.flags)} here, '
+                             f'{int(other.params.flags)} in the other): their classes follow different rules')
         keys, sizes = other._host()
         if len(keys) == 0:
             return np.zeros(0, dtype=np.int64)
@@ -369,28 +404,33 @@ class FoliationRegistry:
 
     # ---- persistence
     def save(self, path):
-        """One .npz: the leaders' fields, keys and sizes, m, tau, min_points and the context's 8
-        grid doubles."""
+        """One .npz: the leaders' fields, keys and sizes, m, tau, min_points, flags and the
+        context's 8 grid doubles."""
         keys, sizes = self._host()
         with open(path, 'wb') as f:
             np.savez(f, fields=self.leader_fields().cpu().numpy(), keys=keys, sizes=sizes,
                      m=np.int64(self.params.m), tau=np.float64(self.params.tau),
-                     min_points=np.int64(self.params.min_points), grid=self.grid)
+                     min_points=np.int64(self.params.min_points), flags=np.int64(self.params.flags),
+                     grid=self.grid)
 
     @classmethod
     def load(cls, ctx, path, params: Optional[FolParams] = None, capacity_hint: int = 0) -> 'FoliationRegistry':
         """A registry on ``ctx`` holding the saved leaders as they were (no re-matching: ids are
-        preserved).  ``params`` (None: the file's) must agree with the file's ``m``, and the file's
-        grid with the context's: otherwise ValueError naming the field."""
+        preserved).  ``params`` (None: the file's) must agree with the file's ``m`` and ``flags`` (a
+        file without ``flags`` was saved with 0), and the file's grid with the context's: otherwise
+        ValueError naming the field."""
         import torch
         with np.load(path) as d:
             fields, keys, sizes = d['fields'], d['keys'], d['sizes']
             m, tau, min_points, grid = int(d['m']), float(d['tau']), int(d['min_points']), d['grid']
+            flags = int(d['flags']) if 'flags' in d.files else 0
         if params is None:
             params = default_fol_params()
-            params.m, params.tau, params.min_points = m, tau, min_points
+            params.m, params.tau, params.min_points, params.flags = m, tau, min_points, flags
         if int(params.m) != m:
             raise ValueError(f'{path}: m = {m} in the file, {int(params.m)} asked for')
+        if (int(params.flags) ^ flags) & FOL_AXIS:
+            raise ValueError(f'{path}: flags = {flags} in the file, {int(params.flags)} asked for')
         reg = cls(ctx, params, max(capacity_hint, len(keys)))
         try:
             if not np.array_equal(reg.grid, grid):
