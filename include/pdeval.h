@@ -334,6 +334,8 @@ typedef struct pdeval_fol_params {
     int32_t flags;       /* PDEVAL_FOL_* bits (0); other bits are ignored                        */
 } pdeval_fol_params;
 #define PDEVAL_FOL_AXIS 1   /* functions of one coordinate form one class per axis (above)       */
+#define PDEVAL_FOL_LINK 2   /* a registry also records the links between its classes (below);
+                               pdeval_jacobian_match and pdeval_foliation_classes ignore it      */
 #define PDEVAL_FOL_MAX_PROBES 32
 int pdeval_default_fol_params(pdeval_fol_params* out);
 /* Device pointers, asynchronous on `stream` (NULL = the context's).  d_mask[row]: bit k set iff
@@ -430,6 +432,53 @@ int pdeval_fol_registry_info(pdeval_fol_registry* reg, pdeval_fol_params* params
 /* count[k] rows more in class class_id[k] (host arrays of n), rows that were classified
  * elsewhere: how the sizes of a merged registry are carried over.                              */
 int pdeval_fol_registry_add_sizes(pdeval_fol_registry* reg, const int64_t* class_id, const int64_t* count, int64_t n);
+
+/* ---- links and components (DESIGN.md §14 "Links and components") ----
+ * The match is a tolerance test on the points two fields have in common, so it is not
+ * transitive: two leaders of one foliation whose finite domains share fewer than min_points
+ * points never match each other, while a row that covers both matches both.  A link {c, l} is an
+ * unordered pair of classes with such a row: a member of c that also matches the leader of l.  A
+ * component is a connected component of the graph of classes and links; component[c] is the
+ * smallest class id in c's component.  Class ids, sizes and leaders do not depend on the links,
+ * and components only ever merge.
+ * Arrival rule (flags & PDEVAL_FOL_LINK, off by default; a registry's flag only): when a row is
+ * assigned, the leaders that exist are those resident before its batch plus the new leaders of
+ * the batch positioned before it.  It joins the first of them it matches, class c, as without
+ * the flag; every other one of them it matches, l, gives the link {c, l}.  A row with class -1
+ * gives none, and neither does a new leader, which matched nothing.  The links of a list do not
+ * depend on how it is cut into batches.  The pass (fol_link_kernel: one launch per batch, a
+ * second one if the batch gave more edges than the edge buffer held; the buffer starts at
+ * max(capacity_hint, 64) pairs and grows by doubling, outside any kernel) runs on the batch's
+ * fields against the store with the batch's new leaders in it, and is planned before the batch
+ * is committed: an error of the call leaves classes, links and components as they were.
+ * With the flag clear no link code runs and every result is what it was.                      */
+/* The explicit pass, with or without the flag: rows the caller still holds (d_fields
+ * [n_rows][2][m^2], device) with their class ids (host, n_rows; -1 = skip the row) against all
+ * current leaders; adds {class_id[r], l} for every leader l != class_id[r] that row r matches,
+ * which completes the links to leaders created after the row.  *n_new_links (may be NULL): links
+ * not known before.  A class id outside [-1, n_classes): PDEVAL_ERR_ARG.                        */
+int pdeval_fol_registry_link_fields(pdeval_ctx* ctx, pdeval_fol_registry* reg, const double* d_fields,
+                                    const int64_t* class_id, int64_t n_rows, int64_t* n_new_links);
+/* Any argument may be NULL.  component (host, n_classes): the smallest class id of each class's
+ * component; *n_components; *n_links: distinct links.                                           */
+int pdeval_fol_registry_components(pdeval_fol_registry* reg, int64_t* component, int64_t* n_components,
+                                   int64_t* n_links);
+/* edges (host, n_links x 2): the links, sorted, deduplicated, the smaller id first.            */
+int pdeval_fol_registry_links(pdeval_fol_registry* reg, int64_t* edges);
+/* Adds n links (host, n x 2, any order, repeats allowed) to the registry's: how saved links are
+ * installed after pdeval_fol_registry_load.  An end outside [0, n_classes) or an edge with equal
+ * ends: PDEVAL_ERR_ARG, nothing added.                                                          */
+int pdeval_fol_registry_load_links(pdeval_fol_registry* reg, const int64_t* edges, int64_t n);
+/* The links of another registry carried over after its leaders were assigned here: each edge
+ * (ids of the other registry, both in [0, n_map), distinct) becomes {id_map[a], id_map[b]}, and is
+ * dropped when both ends landed in one class.  That a merged leader joined an existing class is
+ * no link by itself.  A bad edge or an id_map entry outside [0, n_classes): PDEVAL_ERR_ARG,
+ * nothing added.                                                                                */
+int pdeval_fol_registry_merge_links(pdeval_fol_registry* reg, const int64_t* edges, int64_t n, const int64_t* id_map,
+                                    int64_t n_map);
+/* *link_ms: the device time of the link kernel's launches in the most recent assign or
+ * link_fields call (HIP events; 0 if none ran).                                                 */
+int pdeval_fol_registry_link_ms(pdeval_fol_registry* reg, double* link_ms);
 
 /* Host-side program analysis (no GPU): required stack depth, or < 0 if malformed.      */
 int pdeval_program_depth(const int32_t* ops, int64_t n_words);

@@ -1,11 +1,14 @@
 // pdeval_fol_registry.hip -- the foliation class registry (DESIGN.md §14 "Registry"): the leaders'
 // gradient fields resident on the device across batches, fol_assign_kernel (Stage A: each row's
-// first match among them in one launch), the store's append / export kernel and the
+// first match among them in one launch), fol_link_kernel (the link pass: every other leader a
+// row matches, "Links and components"), the store's append / export kernel and the
 // pdeval_fol_registry_* entry points.  Stage B and the fields reuse pdeval_foliation.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -115,6 +118,104 @@ void launch_fol_assign(const FolAssignArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((fol_assign_kernel<false, true>), grid, block, 0, s, a);
 }
 
+// The link pass (DESIGN.md §14 "Links and components").  The shape of Stage A -- one wave per
+// row, four rows per block, the leaders' first chunks in LDS tiles of T, REG at m <= 16, a pair
+// left at its first bad chunk -- with these differences: a row does not stop at a match, it scans
+// the leaders [0, lim[row]) and skips its own class cls[row], and for every match lane 0 appends
+// the pair (cls[row], leader) to the edge buffer, the slot taken by an atomic add on a device
+// counter; an edge past the buffer's capacity is counted and not stored (the host grows the
+// buffer and repeats the launch).  A row with cls[row] < 0 scans nothing.  The block walks the
+// tiles below the largest lim of its four rows, so the only indices read are row < n_rows and
+// leader < max lim <= L; the host checks lim and cls before the launch.  Edge order is
+// whatever the atomics give; the components do not depend on it.
+template <bool REG, bool AXIS>
+__global__ __launch_bounds__(256) void fol_link_kernel(FolLinkArgs a) {
+    constexpr int T = kFolAssignTile, NR = REG ? kFolRegChunks : 1;
+    constexpr int kPf = T * 2 * kFolChunk / 2 / 256;   // double2 per thread and tile
+    __shared__ double2 tile2[T * kFolChunk];
+    __shared__ int s_lim[4];
+    const double* tile = (const double*)tile2;
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t row = (int64_t)blockIdx.x * 4 + wib;
+    const int mm = a.mm;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const bool in_batch = row < a.n_rows;
+    const double* ra = a.rows + (in_batch ? row : 0) * 2 * (int64_t)mm;
+    const int own = in_batch ? __builtin_amdgcn_readfirstlane(a.cls[row]) : -1;
+    const int lim = own >= 0 ? __builtin_amdgcn_readfirstlane(a.lim[row]) : 0;
+    if (lane == 0) s_lim[wib] = lim;
+    double fa[NR], fb[NR];
+#pragma unroll
+    for (int c = 0; c < NR; ++c) {
+        const int p = c * kFolChunk + lane;
+        const int pc = p < mm ? p : mm - 1;
+        fa[c] = p < mm ? ra[pc] : nan;
+        fb[c] = p < mm ? ra[mm + pc] : nan;
+    }
+    __syncthreads();
+    const int top = max(max(s_lim[0], s_lim[1]), max(s_lim[2], s_lim[3]));   // block-uniform, <= L
+    double2 pf[kPf];
+    auto fetch = [&](int t0) {
+        const int n2 = (top - t0 < T ? top - t0 : T) * kFolChunk;   // double2 of the tile's leaders
+        const double2* src = (const double2*)(a.store + fol_store_at(a.cap, 0, t0));
+#pragma unroll
+        for (int i = 0; i < kPf; ++i) {
+            const int j = (int)threadIdx.x + 256 * i;
+            pf[i] = j < n2 ? src[j] : double2{nan, nan};
+        }
+    };
+    if (top > 0) fetch(0);
+    for (int t0 = 0; t0 < top; t0 += T) {
+#pragma unroll
+        for (int i = 0; i < kPf; ++i) tile2[(int)threadIdx.x + 256 * i] = pf[i];
+        __syncthreads();
+        if (t0 + T < top) fetch(t0 + T);
+        const int tn = lim - t0 < T ? lim - t0 : T;   // (<= 0 for a row whose leaders end before this tile)
+        for (int k = 0; k < tn; ++k) {
+            const int l = t0 + k;
+            if (l == own) continue;
+            const double* q0 = tile + k * 2 * kFolChunk;
+            FolCount n{0, 0};
+            fol_chunk_test<AXIS>(fa[0], fb[0], q0[lane], q0[kFolChunk + lane], lane < mm, a.tau, n);
+            if (n.nb) continue;
+            if constexpr (REG) {
+#pragma unroll
+                for (int c = 1; c < NR; ++c)
+                    if (c < a.n_chunk && !n.nb) {
+                        const double* q = a.store + fol_store_at(a.cap, c, l);
+                        fol_chunk_test<AXIS>(fa[c], fb[c], q[lane], q[kFolChunk + lane], c * kFolChunk + lane < mm,
+                                             a.tau, n);
+                    }
+            } else {
+                for (int c = 1; c < a.n_chunk && !n.nb; ++c) {
+                    const double* q = a.store + fol_store_at(a.cap, c, l);
+                    const int p = c * kFolChunk + lane;
+                    const int pc = p < mm ? p : mm - 1;
+                    fol_chunk_test<AXIS>(ra[pc], ra[mm + pc], q[lane], q[kFolChunk + lane], p < mm, a.tau, n);
+                }
+            }
+            if (n.nu >= a.min_points && n.nb == 0 && lane == 0) {
+                const unsigned long long slot = atomicAdd(a.count, 1ull);
+                if (slot < (unsigned long long)a.ecap) {
+                    a.edges[2 * slot] = own;
+                    a.edges[2 * slot + 1] = l;
+                }
+            }
+        }
+        __syncthreads();   // this tile's readers before the next tile's writers
+    }
+}
+
+void launch_fol_link(const FolLinkArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.n_rows + 3) / 4)), block(256);
+    const bool reg = a.n_chunk <= kFolRegChunks, axis = (a.flags & PDEVAL_FOL_AXIS) != 0;
+    if (reg && !axis) hipLaunchKernelGGL((fol_link_kernel<true, false>), grid, block, 0, s, a);
+    else if (!reg && !axis) hipLaunchKernelGGL((fol_link_kernel<false, false>), grid, block, 0, s, a);
+    else if (reg) hipLaunchKernelGGL((fol_link_kernel<true, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((fol_link_kernel<false, true>), grid, block, 0, s, a);
+}
+
 // One wave per (leader, chunk) of the call.  to_store: leader k's field, fields[idx[k]] (or
 // fields[k]), becomes store leader base + k, NaN at the points past m^2 and throughout for an
 // index outside [0, n_rows); otherwise store leader base + k is written out to fields[k].
@@ -191,6 +292,17 @@ struct pdeval_fol_registry {
     double* d_field = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;   // around Stage A's launch
     bool timed = false;
+    // the link pass (PDEVAL_FOL_LINK, pdeval_fol_registry_link_fields): the rows' classes and scan
+    // limits, link_cap rows; the edge buffer, edge_cap pairs, and its counter; allocated at first use
+    int64_t link_cap = 0, edge_cap = 0, edge_hint = 0;
+    int32_t* d_cls = nullptr;
+    int32_t* d_lim = nullptr;
+    int32_t* d_edges = nullptr;
+    unsigned long long* d_count = nullptr;
+    hipEvent_t e2 = nullptr, e3 = nullptr;   // around each launch of the link kernel
+    double link_ms = 0.0;                    // their sum over the most recent call
+    std::vector<int32_t> cls32, lim32, edges;
+    std::vector<FolBook::Link> merged, fresh;
     // host buffers of a batch, reused
     std::vector<int64_t> first, leader_b, un, new_rows, ids;
     std::vector<int32_t> nfin;
@@ -292,6 +404,136 @@ void reg_move_args(const pdeval_fol_registry* r, FolMoveArgs* a) {
     a->n_chunk = r->n_chunk;
 }
 
+// the buffers of a link pass over n rows; the edge buffer holds at least `edges` pairs
+int reg_link_scratch(pdeval_fol_registry* r, int64_t n, int64_t edges) {
+    if (n > r->link_cap) {
+        int32_t* d_cls = nullptr;
+        int32_t* d_lim = nullptr;
+        if (hipMalloc((void**)&d_cls, (size_t)n * sizeof(int32_t)) != hipSuccess ||
+            hipMalloc((void**)&d_lim, (size_t)n * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(d_cls);
+            return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the link pass's row buffers");
+        }
+        (void)hipFree(r->d_cls);
+        (void)hipFree(r->d_lim);
+        r->d_cls = d_cls;
+        r->d_lim = d_lim;
+        r->link_cap = n;
+    }
+    if (!r->d_count && hipMalloc((void**)&r->d_count, sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        r->d_count = nullptr;
+        return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the edge counter");
+    }
+    if (edges > r->edge_cap) {
+        const int64_t cap = fol_next_capacity(r->edge_cap, edges);
+        int32_t* d_edges = nullptr;
+        if (hipMalloc((void**)&d_edges, (size_t)cap * 2 * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fol_fail(r->ctx, PDEVAL_ERR_ALLOC,
+                            ("pdeval_fol_registry: cannot allocate an edge buffer of " + std::to_string(cap) + " pairs").c_str());
+        }
+        (void)hipFree(r->d_edges);
+        r->d_edges = d_edges;
+        r->edge_cap = cap;
+    }
+    return PDEVAL_OK;
+}
+
+// The link pass over the rows d_fields with the classes r->cls32 and the limits r->lim32 against
+// the store's leaders [0, L) (the book may still hold fewer: a batch is linked before it is
+// committed, so that a failure here leaves classes and components as they were).  Leaves the
+// planned links in r->merged / r->fresh; nothing of the book has changed.
+int reg_link(pdeval_fol_registry* r, const double* d_fields, int64_t n, int64_t L) {
+    pdeval_ctx* c = r->ctx;
+    const hipStream_t s = r->v.stream;
+    r->link_ms = 0.0;
+    r->edges.clear();
+    if (L > INT32_MAX) return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry: the link pass holds class ids in 32 bits");
+    if (!FolBook::link_rows_ok(r->cls32.data(), r->lim32.data(), n, L))
+        return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry: a class id or a scan limit of the link pass outside the registry");
+    if (n > 0 && L > 1) {
+        int rc = reg_link_scratch(r, n, std::max<int64_t>(r->edge_hint, 1));
+        if (rc != PDEVAL_OK) return rc;
+        hipError_t e;
+        if ((e = hipMemcpyAsync(r->d_cls, r->cls32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess ||
+            (e = hipMemcpyAsync(r->d_lim, r->lim32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess)
+            return fol_hip_fail(c, "hipMemcpyAsync", e);
+        // at most two launches: the second with a buffer that holds what the first counted
+        for (int pass = 0; pass < 2; ++pass) {
+            FolLinkArgs a{};
+            a.rows = d_fields;
+            a.n_rows = n;
+            a.cls = r->d_cls;
+            a.lim = r->d_lim;
+            a.store = r->d_store;
+            a.cap = r->cap;
+            a.L = L;
+            a.mm = r->mm;
+            a.n_chunk = r->n_chunk;
+            a.tau = r->prm.tau;
+            a.min_points = r->prm.min_points;
+            a.edges = r->d_edges;
+            a.ecap = r->edge_cap;
+            a.count = r->d_count;
+            a.flags = (uint32_t)r->prm.flags;
+            if ((e = hipMemsetAsync(r->d_count, 0, sizeof(unsigned long long), s)) != hipSuccess)
+                return fol_hip_fail(c, "hipMemsetAsync", e);
+            (void)hipEventRecord(r->e2, s);
+            launch_fol_link(a, s);
+            if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_link_kernel", e);
+            (void)hipEventRecord(r->e3, s);
+            unsigned long long count = 0;
+            if ((e = hipMemcpyAsync(&count, r->d_count, sizeof(count), hipMemcpyDeviceToHost, s)) != hipSuccess)
+                return fol_hip_fail(c, "hipMemcpyAsync", e);
+            if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "fol_link_kernel", e);
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, r->e2, r->e3) != hipSuccess) (void)hipGetLastError();
+            else r->link_ms += ms;
+            // (a row yields at most one edge per leader other than its own)
+            if (count > (unsigned long long)n * (unsigned long long)(L - 1))
+                return fol_fail(c, PDEVAL_ERR_HIP, "pdeval_fol_registry: fol_link_kernel counted more edges than pairs");
+            if ((int64_t)count > r->edge_cap) {
+                if (pass == 1)
+                    return fol_fail(c, PDEVAL_ERR_HIP, "pdeval_fol_registry: fol_link_kernel counted more edges the second time");
+                if ((rc = reg_link_scratch(r, n, (int64_t)count)) != PDEVAL_OK) return rc;
+                continue;
+            }
+            try {
+                r->edges.resize((size_t)count * 2);
+            } catch (const std::bad_alloc&) {
+                return fol_fail(c, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the host copy of the edges");
+            }
+            if (count > 0) {
+                if ((e = hipMemcpyAsync(r->edges.data(), r->d_edges, (size_t)count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+                    return fol_hip_fail(c, "hipMemcpyAsync", e);
+                if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "hipMemcpyAsync", e);
+            }
+            break;
+        }
+    }
+    try {
+        if (!r->book.plan_links(r->edges.data(), (int64_t)r->edges.size() / 2, L, r->merged, r->fresh))
+            return fol_fail(c, PDEVAL_ERR_HIP, "pdeval_fol_registry: fol_link_kernel returned an edge outside the registry");
+    } catch (const std::bad_alloc&) {
+        return fol_fail(c, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the links");
+    }
+    return PDEVAL_OK;
+}
+
+// edges of a caller (load_links, merge_links) planned and committed; bad: the text of PDEVAL_ERR_ARG
+int reg_add_links(pdeval_fol_registry* r, const int64_t* edges, int64_t n, const char* bad) {
+    try {
+        if (!r->book.plan_links(edges, n, r->book.n_classes(), r->merged, r->fresh))
+            return fol_fail(r->ctx, PDEVAL_ERR_ARG, bad);
+    } catch (const std::bad_alloc&) {
+        return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the links");
+    }
+    r->book.commit_links(r->merged, r->fresh);
+    return PDEVAL_OK;
+}
+
 // Stage A, Stage B and the append on the fields of a batch; d_nfin: their finite counts
 int reg_assign(pdeval_fol_registry* r, const double* d_fields, const int32_t* d_nfin, int64_t n, const int64_t* keys,
                int64_t* class_id, int64_t* n_new) {
@@ -358,7 +600,15 @@ int reg_assign(pdeval_fol_registry* r, const double* d_fields, const int32_t* d_
         if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
     }
+    // the link pass (PDEVAL_FOL_LINK): the batch's rows, by the arrival rule, against the store as
+    // the batch leaves it; planned before the commit, committed with it
+    const bool link = (r->prm.flags & PDEVAL_FOL_LINK) != 0;
+    if (link) {
+        FolBook::arrival_limits(r->ids.data(), n, L, r->new_rows, r->cls32, r->lim32);
+        if ((rc = reg_link(r, d_fields, n, L + classes)) != PDEVAL_OK) return rc;
+    }
     r->book.commit(r->ids.data(), n, keys, r->new_rows);
+    if (link) r->book.commit_links(r->merged, r->fresh);
     std::copy(r->ids.begin(), r->ids.end(), class_id);
     if (n_new) *n_new = classes;
     return PDEVAL_OK;
@@ -381,14 +631,20 @@ extern "C" int pdeval_fol_registry_create(pdeval_ctx* c, const pdeval_fol_params
     r->prm = prm;
     r->mm = prm.m * prm.m;
     r->n_chunk = (r->mm + kFolChunk - 1) / kFolChunk;
-    if ((e = hipEventCreate(&r->e0)) != hipSuccess || (e = hipEventCreate(&r->e1)) != hipSuccess) {
+    r->edge_hint = std::max<int64_t>(capacity_hint, kFolEdgeMin);
+    if ((e = hipEventCreate(&r->e0)) != hipSuccess || (e = hipEventCreate(&r->e1)) != hipSuccess ||
+        (e = hipEventCreate(&r->e2)) != hipSuccess || (e = hipEventCreate(&r->e3)) != hipSuccess) {
         if (r->e0) (void)hipEventDestroy(r->e0);
+        if (r->e1) (void)hipEventDestroy(r->e1);
+        if (r->e2) (void)hipEventDestroy(r->e2);
         delete r;
         return fol_hip_fail(c, "hipEventCreate", e);
     }
     if ((rc = reg_reserve(r, std::max<int64_t>(capacity_hint, 1))) != PDEVAL_OK) {
         (void)hipEventDestroy(r->e0);
         (void)hipEventDestroy(r->e1);
+        (void)hipEventDestroy(r->e2);
+        (void)hipEventDestroy(r->e3);
         delete r;
         return rc;
     }
@@ -405,8 +661,14 @@ extern "C" int pdeval_fol_registry_destroy(pdeval_fol_registry* r) {
     (void)hipFree(r->d_idx);
     (void)hipFree(r->d_mask);
     (void)hipFree(r->d_field);
+    (void)hipFree(r->d_cls);
+    (void)hipFree(r->d_lim);
+    (void)hipFree(r->d_edges);
+    (void)hipFree(r->d_count);
     (void)hipEventDestroy(r->e0);
     (void)hipEventDestroy(r->e1);
+    (void)hipEventDestroy(r->e2);
+    (void)hipEventDestroy(r->e3);
     delete r;
     return PDEVAL_OK;
 }
@@ -561,5 +823,82 @@ extern "C" int pdeval_fol_registry_add_sizes(pdeval_fol_registry* r, const int64
     if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_add_sizes: null registry");
     if (n < 0 || (n > 0 && (!class_id || !count)) || !r->book.add_sizes(class_id, count, n))
         return fol_fail(r->ctx, PDEVAL_ERR_ARG, "pdeval_fol_registry_add_sizes: bad argument (a class outside the registry or a negative count)");
+    return PDEVAL_OK;
+}
+
+extern "C" int pdeval_fol_registry_link_fields(pdeval_ctx* c, pdeval_fol_registry* r, const double* d_fields,
+                                               const int64_t* class_id, int64_t n_rows, int64_t* n_new_links) {
+    int rc = reg_check(c, r, "pdeval_fol_registry_link_fields");
+    if (rc != PDEVAL_OK) return rc;
+    if (n_new_links) *n_new_links = 0;
+    if (n_rows < 0 || n_rows > PDEVAL_MAX_BATCH || (n_rows > 0 && (!d_fields || !class_id)))
+        return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry_link_fields: bad argument");
+    const int64_t L = r->book.n_classes();
+    for (int64_t k = 0; k < n_rows; ++k)
+        if (class_id[k] < -1 || class_id[k] >= L)
+            return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry_link_fields: a class id outside [-1, n_classes)");
+    if (n_rows == 0) return PDEVAL_OK;
+    hipError_t e = hipSetDevice(r->v.device);
+    if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
+    r->cls32.resize((size_t)n_rows);
+    r->lim32.resize((size_t)n_rows);
+    for (int64_t k = 0; k < n_rows; ++k) {
+        r->cls32[(size_t)k] = (int32_t)class_id[k];
+        r->lim32[(size_t)k] = class_id[k] < 0 ? 0 : (int32_t)std::min<int64_t>(L, INT32_MAX);
+    }
+    if ((rc = reg_link(r, d_fields, n_rows, L)) != PDEVAL_OK) return rc;
+    if (n_new_links) *n_new_links = (int64_t)r->fresh.size();
+    r->book.commit_links(r->merged, r->fresh);
+    return PDEVAL_OK;
+}
+
+extern "C" int pdeval_fol_registry_components(pdeval_fol_registry* r, int64_t* component, int64_t* n_components,
+                                              int64_t* n_links) {
+    if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_components: null registry");
+    const int64_t L = r->book.n_classes();
+    for (int64_t k = 0; component && k < L; ++k) component[k] = r->book.component(k);
+    if (n_components) *n_components = r->book.n_components();
+    if (n_links) *n_links = (int64_t)r->book.links.size();
+    return PDEVAL_OK;
+}
+
+extern "C" int pdeval_fol_registry_links(pdeval_fol_registry* r, int64_t* edges) {
+    if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_links: null registry");
+    if (!edges && !r->book.links.empty())
+        return fol_fail(r->ctx, PDEVAL_ERR_ARG, "pdeval_fol_registry_links: bad argument");
+    for (size_t k = 0; k < r->book.links.size(); ++k) {
+        edges[2 * k] = r->book.links[k].first;
+        edges[2 * k + 1] = r->book.links[k].second;
+    }
+    return PDEVAL_OK;
+}
+
+extern "C" int pdeval_fol_registry_load_links(pdeval_fol_registry* r, const int64_t* edges, int64_t n) {
+    if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_load_links: null registry");
+    if (n < 0 || (n > 0 && !edges)) return fol_fail(r->ctx, PDEVAL_ERR_ARG, "pdeval_fol_registry_load_links: bad argument");
+    return reg_add_links(r, edges, n,
+                         "pdeval_fol_registry_load_links: an edge with an end outside [0, n_classes) or with equal ends");
+}
+
+extern "C" int pdeval_fol_registry_merge_links(pdeval_fol_registry* r, const int64_t* edges, int64_t n,
+                                               const int64_t* id_map, int64_t n_map) {
+    if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_merge_links: null registry");
+    if (n < 0 || n_map < 0 || (n > 0 && (!edges || !id_map)))
+        return fol_fail(r->ctx, PDEVAL_ERR_ARG, "pdeval_fol_registry_merge_links: bad argument");
+    std::vector<int64_t> mapped;
+    try {
+        if (!FolBook::map_links(edges, n, id_map, n_map, mapped))
+            return fol_fail(r->ctx, PDEVAL_ERR_ARG,
+                            "pdeval_fol_registry_merge_links: an edge with an end outside [0, n_map) or with equal ends");
+    } catch (const std::bad_alloc&) {
+        return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the links");
+    }
+    return reg_add_links(r, mapped.data(), (int64_t)mapped.size() / 2,
+                         "pdeval_fol_registry_merge_links: the id map names a class outside [0, n_classes)");
+}
+
+extern "C" int pdeval_fol_registry_link_ms(pdeval_fol_registry* r, double* link_ms) {
+    if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_link_ms: null registry");
+    if (link_ms) *link_ms = r->link_ms;
     return PDEVAL_OK;
 }

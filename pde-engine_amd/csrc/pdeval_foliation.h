@@ -182,6 +182,7 @@ inline int fol_round(const uint32_t* mask, const int64_t* un, int64_t nu, int np
 constexpr int kFolChunk = 64;
 constexpr int kFolAssignTile = 32;   // leaders per LDS tile of fol_assign_kernel (T)
 constexpr int kFolRegChunks = 4;     // chunks of a row held in registers: m <= 16
+constexpr int kFolEdgeMin = 64;      // pairs the link pass's edge buffer holds at least (it grows by doubling)
 PD_HD int64_t fol_store_at(int64_t cap, int chunk, int64_t leader) {
     return ((int64_t)chunk * cap + leader) * (2 * kFolChunk);
 }
@@ -274,6 +275,26 @@ struct FolAssignArgs {
     uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernel's AXIS instantiations
 };
 void launch_fol_assign(const FolAssignArgs& a, hipStream_t s);
+
+// The link pass of a registry (pdeval_fol_registry.hip, DESIGN.md §14 "Links and components"):
+// for every leader l < lim[row], l != cls[row], that the row matches, the pair (cls[row], l) is
+// appended to edges.  A row with cls[row] < 0 yields none.
+struct FolLinkArgs {
+    const double* rows;        // row fields, [n_rows][2][mm]
+    int64_t n_rows;
+    const int32_t* cls;        // n_rows, each -1 or in [0, L) (checked by the host before the launch)
+    const int32_t* lim;        // n_rows, each in [0, L] (likewise)
+    const double* store;       // the leader store, chunk-major (fol_store_at)
+    int64_t cap, L;            // its capacity and the leaders it holds
+    int mm, n_chunk;
+    double tau;
+    int min_points;
+    int32_t* edges;            // [ecap][2]
+    int64_t ecap;
+    unsigned long long* count; // edges found, zeroed by the caller; those past ecap are counted, not stored
+    uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernel's AXIS instantiations
+};
+void launch_fol_link(const FolLinkArgs& a, hipStream_t s);
 
 // rows of [.][2][mm] fields into the store (append, load) or the store's leaders out to
 // [L][2][mm] (leaders): one wave per (leader, chunk)

@@ -33,6 +33,8 @@ EXPORTS = (
     'pdeval_fol_registry_assign_fields', 'pdeval_fol_registry_size', 'pdeval_fol_registry_leaders',
     'pdeval_fol_registry_load', 'pdeval_fol_registry_info', 'pdeval_fol_registry_add_sizes',
     'pdeval_field_kinds', 'pdeval_fol_registry_kinds',
+    'pdeval_fol_registry_link_fields', 'pdeval_fol_registry_components', 'pdeval_fol_registry_links',
+    'pdeval_fol_registry_load_links', 'pdeval_fol_registry_merge_links', 'pdeval_fol_registry_link_ms',
 )
 MAX_BATCH = 1 << 30          # PDEVAL_MAX_BATCH
 UNIQUE_ID_BYTES = 128
@@ -43,6 +45,7 @@ LIST_NAMES = ('defer_stack3', 'complex', 'defer_stack8', 'tier2', 'tier2_stack3'
 N_PASSES = 12
 FOL_MAX_PROBES = 32          # PDEVAL_FOL_MAX_PROBES
 FOL_AXIS = 1                 # PDEVAL_FOL_AXIS: functions of one coordinate form one class per axis
+FOL_LINK = 2                 # PDEVAL_FOL_LINK: a registry records the links between its classes
 
 
 class Params(C.Structure):
@@ -73,7 +76,7 @@ class KerrConstants(C.Structure):
 
 class FolParams(C.Structure):
     """pdeval_fol_params (include/pdeval.h): the Jacobian test on an m x m sample grid; ``flags``
-    holds the PDEVAL_FOL_* bits (``FOL_AXIS``)."""
+    holds the PDEVAL_FOL_* bits (``FOL_AXIS``, ``FOL_LINK``)."""
     _fields_ = [('tau', C.c_double), ('m', C.c_int32), ('min_points', C.c_int32), ('flags', C.c_int32)]
 
 
@@ -146,6 +149,12 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_fol_registry_add_sizes.argtypes = [vp, vp, vp, i64]
     lib.pdeval_field_kinds.argtypes = [vp, vp, i64, C.POINTER(FolParams), vp, vp]
     lib.pdeval_fol_registry_kinds.argtypes = [vp, vp]
+    lib.pdeval_fol_registry_link_fields.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
+    lib.pdeval_fol_registry_components.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    lib.pdeval_fol_registry_links.argtypes = [vp, vp]
+    lib.pdeval_fol_registry_load_links.argtypes = [vp, vp, i64]
+    lib.pdeval_fol_registry_merge_links.argtypes = [vp, vp, i64, vp, i64]
+    lib.pdeval_fol_registry_link_ms.argtypes = [vp, C.POINTER(dbl)]
     if path is None:
         _lib = lib
     return lib
@@ -163,13 +172,16 @@ def default_fol_params() -> FolParams:
     return p
 
 
-def fol_params(params: Optional[FolParams] = None, axis: Optional[bool] = None) -> FolParams:
+def fol_params(params: Optional[FolParams] = None, axis: Optional[bool] = None,
+               link: Optional[bool] = None) -> FolParams:
     """A copy of ``params`` (None: the defaults); ``axis`` True / False sets / clears ``FOL_AXIS``
-    in its flags, None leaves them."""
+    in its flags and ``link`` ``FOL_LINK`` (a registry's flag), None leaves them."""
     src = params if params is not None else default_fol_params()
     p = FolParams(src.tau, src.m, src.min_points, src.flags)
     if axis is not None:
         p.flags = (int(p.flags) | FOL_AXIS) if axis else (int(p.flags) & ~FOL_AXIS)
+    if link is not None:
+        p.flags = (int(p.flags) | FOL_LINK) if link else (int(p.flags) & ~FOL_LINK)
     return p
 
 

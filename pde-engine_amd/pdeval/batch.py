@@ -852,19 +852,29 @@ class BatchValidator:
             tags = F.tag_known(self.ctx, self.pd, classes, (d_ops, n_words, d_off, n), params)
         return classes, accepted, tags
 
-    def foliation_registry(self, params=None, capacity_hint: int = 0, axis=None):
+    def foliation_registry(self, params=None, capacity_hint: int = 0, axis=None, link=None):
         """A ``pdeval.foliation.FoliationRegistry`` on this validator's context (force-free): the
         streaming caller holds it next to the validator and passes it to ``assign_foliation``, which
         follows the registry's parameters.  The axis rule is taken from ``params.flags``
-        (``FOL_AXIS``); ``axis=True`` / ``False`` sets / clears it."""
+        (``FOL_AXIS``); ``axis=True`` / ``False`` sets / clears it, and ``link`` likewise ``FOL_LINK``
+        (the registry records the links between its classes; ``foliation_components``)."""
         if self.pd.problem_id != PROBLEM_FORCE_FREE:
             raise ValueError('foliation classes are a force-free notion (the Kerr equation is linear: '
                              'u -> f(u) is no symmetry of it)')
-        if axis is not None:
+        if axis is not None or link is not None:
             from .foliation import fol_params
-            params = fol_params(params, axis)
+            params = fol_params(params, axis, link)
         with self._lock:
             return self.ctx.fol_registry(params, capacity_hint)
+
+    def foliation_components(self, registry):
+        """``registry.components()`` under this validator's lock: int64[n_classes], the smallest
+        class id of each class's component (the classes a link joins, DESIGN.md §14 "Links and
+        components")."""
+        if registry.ctx is not self.ctx:
+            raise ValueError('foliation_components: the registry belongs to another validator\'s context')
+        with self._lock:
+            return registry.components()
 
     def assign_foliation(self, registry, strings: Sequence[str], keys=None):
         """One batch of a stream into ``registry`` (``foliation_registry``): compiles and validates

@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import FOL_AXIS, FOL_MAX_PROBES, FolParams, default_fol_params, fol_params  # noqa: F401
+from ._lib import FOL_AXIS, FOL_LINK, FOL_MAX_PROBES, FolParams, default_fol_params, fol_params  # noqa: F401
 
 
 @dataclass
@@ -206,7 +206,14 @@ class FoliationRegistry:
     gives the class ids :func:`classify` gives on the whole list.  Without ``FOL_AXIS`` in the
     flags of ``params`` a function of one coordinate matches nothing, not even itself, so each such
     row is a leader; with it they form one class per axis.  Calls are synchronous, on the context's stream; close the registry before its
-    context."""
+    context.
+
+    The match is not transitive, so two classes can hold the same foliation: their leaders share
+    too few finite points to match each other while a row that covers both matches both.  With
+    ``FOL_LINK`` in the flags every assigned row also records a link between its class and every
+    other leader it matches among those that existed when it arrived; :meth:`link_fields` does the
+    same against all current leaders for rows the caller still holds, with or without the flag.
+    :meth:`components` joins the linked classes; ids, sizes and leaders never depend on it."""
 
     def __init__(self, ctx, params: Optional[FolParams] = None, capacity_hint: int = 0):
         import ctypes as C
@@ -300,6 +307,68 @@ class FoliationRegistry:
         self.last_new = int(n_new.value)
         return cls
 
+    # ---- links and components
+    def link_fields(self, fields, class_ids) -> int:
+        """Tests ``fields`` (a torch float64 tensor [rows, 2, m*m] on the context's device) against
+        all current leaders and adds the link ``{class_ids[r], l}`` for every leader ``l`` other
+        than its own that row ``r`` matches (``class_ids``: what ``assign`` returned for these rows;
+        -1 skips the row).  Returns the number of links that were not known before."""
+        import ctypes as C
+        import torch
+        dev = _device(self.ctx)
+        if fields.dtype != torch.float64 or fields.dim() != 3 or tuple(fields.shape[1:]) != (2, self.mm) \
+                or fields.device != dev:
+            raise ValueError(f'fields: expected a float64 tensor [rows, 2, {self.mm}] on {dev}')
+        fields = fields.contiguous()
+        rows = int(fields.shape[0])
+        ids = np.ascontiguousarray(class_ids, dtype=np.int64)
+        if ids.shape != (rows,):
+            raise ValueError(f'class_ids: expected {rows} entries, got shape {ids.shape}')
+        torch.cuda.current_stream(dev).synchronize()
+        n_new = C.c_int64(0)
+        self._call(self.lib.pdeval_fol_registry_link_fields(self.ctx.h, self.h, fields.data_ptr() or None,
+                                                            ids.ctypes.data, rows, C.byref(n_new)))
+        return int(n_new.value)
+
+    def _components(self):
+        import ctypes as C
+        comp = np.zeros(self.n_classes, dtype=np.int64)
+        nc, nl = C.c_int64(0), C.c_int64(0)
+        self._call(self.lib.pdeval_fol_registry_components(self.h, comp.ctypes.data, C.byref(nc), C.byref(nl)))
+        return comp, int(nc.value), int(nl.value)
+
+    def components(self) -> np.ndarray:
+        """int64[n_classes]: the smallest class id of each class's component (the classes joined by
+        links, directly or through others).  Without links every class is its own component."""
+        return self._components()[0]
+
+    @property
+    def n_components(self) -> int:
+        return self._components()[1]
+
+    @property
+    def n_links(self) -> int:
+        return self._components()[2]
+
+    def links(self) -> np.ndarray:
+        """int64[n_links, 2]: the links, sorted, deduplicated, the smaller class id first."""
+        edges = np.zeros((self.n_links, 2), dtype=np.int64)
+        self._call(self.lib.pdeval_fol_registry_links(self.h, edges.ctypes.data))
+        return edges
+
+    def component_sizes(self) -> dict:
+        """{component_id: rows}: the class sizes summed per component."""
+        comp, sizes = self.components(), self.sizes
+        return {int(c): int(sizes[comp == c].sum()) for c in np.unique(comp)}
+
+    @property
+    def link_ms(self) -> float:
+        """Device time of the link kernel's launches in the most recent assign or link_fields call."""
+        import ctypes as C
+        ms = C.c_double(0.0)
+        self._call(self.lib.pdeval_fol_registry_link_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- what the registry holds
     def _size(self):
         import ctypes as C
@@ -357,11 +426,12 @@ class FoliationRegistry:
             self._call(self.lib.pdeval_fol_registry_leaders(self.h, out.data_ptr(), None, None))
         return out
 
-    def tags(self, pd_):
+    def tags(self, pd_, by_component: bool = False):
         """{class_id: name} of the classes that re-parametrise one of ``pd_.known_solutions``, by
         the two rules of :func:`tag_known` applied to the leaders' fields: the leader matches the
         known solution under the Jacobian test, or its field equals the known one's at every
-        sample point."""
+        sample point.  ``by_component``: {component_id: name} instead; a component is named if any
+        of its classes is, and if several names apply the first in ``known_solutions`` order wins."""
         import torch
         from . import problem_defs as P
         if self.n_classes == 0:
@@ -379,6 +449,11 @@ class FoliationRegistry:
             if bool(torch.isfinite(kf).any()):
                 same = (lead_fields == kf) | (torch.isnan(lead_fields) & torch.isnan(kf))
                 hit[:, k] |= same.flatten(1).all(1).cpu().numpy()
+        if by_component:
+            comp = self.components()
+            chit = np.zeros((len(hit), len(names)), dtype=bool)
+            np.logical_or.at(chit, comp, hit)
+            return {int(c): names[int(np.argmax(chit[c]))] for c in np.unique(comp) if chit[c].any()}
         return {int(c): names[int(np.argmax(hit[c]))] for c in range(len(hit)) if hit[c].any()}
 
     def merge(self, other: 'FoliationRegistry') -> np.ndarray:
@@ -387,28 +462,34 @@ class FoliationRegistry:
         class of this registry it matches or becomes a new one (keeping its key) -- and
         ``other``'s class sizes are added.  Returns the int64 map from ``other``'s class ids to
         this registry's.  Members of ``other``'s classes follow their leader without being
-        tested again.  ``other`` is left as it is and may live on another context of the same
-        device, with the same m, grid and flags."""
+        tested again.  ``other``'s links are carried over through the returned map (a link whose
+        ends land in one class here is dropped); with ``FOL_LINK`` the merged leaders also link by
+        the arrival rule, as rows assigned here.  ``other`` is left as it is and may live on another
+        context of the same device, with the same m, grid and flags."""
         if int(other.params.m) != int(self.params.m) or not np.array_equal(other.grid, self.grid):
             raise ValueError('merge: the registries differ in m or grid')
-        if (int(other.params.flags) ^ int(self.params.flags)) & FOL_AXIS:
+        if (int(other.params.flags) ^ int(self.params.flags)) & (FOL_AXIS | FOL_LINK):
             raise ValueError(f'merge: the registries differ in flags ({int(self.params.flags)} here, '
                              f'{int(other.params.flags)} in the other): their classes follow different rules')
         keys, sizes = other._host()
         if len(keys) == 0:
             return np.zeros(0, dtype=np.int64)
+        edges = np.ascontiguousarray(other.links())
         ids = self.assign_fields(other.leader_fields(), keys=keys)
         extra = sizes - 1
         self._call(self.lib.pdeval_fol_registry_add_sizes(self.h, ids.ctypes.data, extra.ctypes.data, len(ids)))
+        if len(edges):
+            self._call(self.lib.pdeval_fol_registry_merge_links(self.h, edges.ctypes.data, len(edges), ids.ctypes.data,
+                                                                len(ids)))
         return ids
 
     # ---- persistence
     def save(self, path):
-        """One .npz: the leaders' fields, keys and sizes, m, tau, min_points, flags and the
-        context's 8 grid doubles."""
+        """One .npz: the leaders' fields, keys and sizes, the links, m, tau, min_points, flags and
+        the context's 8 grid doubles."""
         keys, sizes = self._host()
         with open(path, 'wb') as f:
-            np.savez(f, fields=self.leader_fields().cpu().numpy(), keys=keys, sizes=sizes,
+            np.savez(f, fields=self.leader_fields().cpu().numpy(), keys=keys, sizes=sizes, links=self.links(),
                      m=np.int64(self.params.m), tau=np.float64(self.params.tau),
                      min_points=np.int64(self.params.min_points), flags=np.int64(self.params.flags),
                      grid=self.grid)
@@ -418,18 +499,19 @@ class FoliationRegistry:
         """A registry on ``ctx`` holding the saved leaders as they were (no re-matching: ids are
         preserved).  ``params`` (None: the file's) must agree with the file's ``m`` and ``flags`` (a
         file without ``flags`` was saved with 0), and the file's grid with the context's: otherwise
-        ValueError naming the field."""
+        ValueError naming the field.  A file without ``links`` has none."""
         import torch
         with np.load(path) as d:
             fields, keys, sizes = d['fields'], d['keys'], d['sizes']
             m, tau, min_points, grid = int(d['m']), float(d['tau']), int(d['min_points']), d['grid']
             flags = int(d['flags']) if 'flags' in d.files else 0
+            links = d['links'] if 'links' in d.files else np.zeros((0, 2), dtype=np.int64)
         if params is None:
             params = default_fol_params()
             params.m, params.tau, params.min_points, params.flags = m, tau, min_points, flags
         if int(params.m) != m:
             raise ValueError(f'{path}: m = {m} in the file, {int(params.m)} asked for')
-        if (int(params.flags) ^ flags) & FOL_AXIS:
+        if (int(params.flags) ^ flags) & (FOL_AXIS | FOL_LINK):
             raise ValueError(f'{path}: flags = {flags} in the file, {int(params.flags)} asked for')
         reg = cls(ctx, params, max(capacity_hint, len(keys)))
         try:
@@ -443,6 +525,11 @@ class FoliationRegistry:
             sizes = np.ascontiguousarray(sizes, dtype=np.int64)
             torch.cuda.current_stream(dev).synchronize()
             reg._load(d_f, keys, sizes)
+            links = np.ascontiguousarray(links, dtype=np.int64)
+            if links.ndim != 2 or links.shape[1] != 2:
+                raise ValueError(f'{path}: links {links.shape} are not pairs')
+            if len(links):
+                reg._call(reg.lib.pdeval_fol_registry_load_links(reg.h, links.ctypes.data, len(links)))
         except Exception:
             reg.close()
             raise

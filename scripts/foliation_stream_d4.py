@@ -15,9 +15,13 @@ JSON line, also written to --out.  With --axis everything is measured a second t
 process with the axis rule (PDEVAL_FOL_AXIS: the functions of one coordinate form one class per
 axis) and reported under "axis", next to the figures without it; "leader_kinds" counts the
 registry's leaders that are functions of rho alone or of z alone, "paper_classes" the rows of the
-classes tagged with a paper solution.
+classes tagged with a paper solution.  With --link (combinable with --axis) the stream is measured
+once more with PDEVAL_FOL_LINK under "link" (and "axis_link"): the link pass's device time per batch
+(HIP events around its launches, "link_ms"), the number of links and components, the ten largest
+components, "paper_component_counts" (how many components carry each paper name) and the
+components that hold classes tagged with two different paper names.
 
-    python scripts/foliation_stream_d4.py --axis --out foliation_stream_d4.json
+    python scripts/foliation_stream_d4.py --axis --link --out foliation_stream_d4.json
 """
 import argparse
 import json
@@ -33,7 +37,7 @@ import torch  # noqa: E402
 
 from pdeval import foliation as FOL  # noqa: E402
 from pdeval import problem_defs as P  # noqa: E402
-from pdeval._lib import FOL_MAX_PROBES, Context, default_fol_params, fol_params  # noqa: E402
+from pdeval._lib import FOL_LINK, FOL_MAX_PROBES, Context, default_fol_params, fol_params  # noqa: E402
 from pdeval.opcodes import CLS_ACCEPT  # noqa: E402
 
 
@@ -44,6 +48,7 @@ def main():
     ap.add_argument('--batch', type=int, default=4096)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--axis', action='store_true', help='also measure with the axis rule (PDEVAL_FOL_AXIS)')
+    ap.add_argument('--link', action='store_true', help='also measure with the link pass (PDEVAL_FOL_LINK)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -94,6 +99,8 @@ def main():
                 ids.append(part)
                 per.append({'rows': int(b1 - b0), 'L_before': int(L), 'stage_a_ms': round(reg.stage_a_ms, 4),
                             'assign_ms': round(ms, 4), 'new': int(reg.last_new)})
+                if linked:
+                    per[-1]['link_ms'] = round(reg.link_ms, 4)
             n_classes = reg.n_classes
             if keep is not None:     # the last, untimed pass: what the registry holds
                 kinds, sizes = reg.kinds(), reg.sizes
@@ -103,10 +110,27 @@ def main():
                     paper_n[name] = paper_n.get(name, 0) + 1
                 extra.update(leader_kinds={'rho_axis': int((kinds == 1).sum()), 'z_axis': int((kinds == 2).sum())},
                              paper_classes=paper, paper_class_counts=paper_n)
+                if linked:
+                    comp = reg.components()
+                    csize = reg.component_sizes()
+                    names = {}
+                    for c, name in reg.tags(pd_).items():
+                        names.setdefault(int(comp[c]), set()).add(name)
+                    comp_n = {}
+                    for name in reg.tags(pd_, by_component=True).values():
+                        comp_n[name] = comp_n.get(name, 0) + 1
+                    top = sorted(csize.items(), key=lambda kv: (-kv[1], kv[0]))[:10]
+                    extra['links'] = {
+                        'links': int(reg.n_links), 'components': int(reg.n_components),
+                        'largest_components': [{'component': c, 'rows': r, 'classes': int((comp == c).sum()),
+                                                'names': sorted(names.get(c, ()))} for c, r in top],
+                        'paper_component_counts': comp_n,
+                        'two_names': {str(c): sorted(v) for c, v in names.items() if len(v) > 1}}
             reg.close()
             return np.concatenate(ids), per, n_classes
 
         loop, extra = {}, {}
+        linked = bool(int(prm.flags) & FOL_LINK)
 
         def block_loop(reg, b0, b1):
             """The last batch against the resident leaders by fol_match_kernel, 32 leaders a launch."""
@@ -144,6 +168,10 @@ def main():
                            'block32_over_stage_a': loop['ms'] / last['stage_a_ms'] if last['stage_a_ms'] else None,
                            'first_equal': bool(np.array_equal(loop['first'], first_a))},
         }
+        if linked:
+            res.update(extra['links'])
+            res['link_total_ms'] = sum(b['link_ms'] for b in per)
+            res['link_over_stage_a'] = res['link_total_ms'] / res['stage_a_total_ms'] if res['stage_a_total_ms'] else None
         return res, equal
 
     out = {
@@ -156,6 +184,12 @@ def main():
     if a.axis:
         out['axis'], equal_axis = measure(fol_params(prm0, axis=True))
         equal = equal and equal_axis
+    if a.link:
+        out['link'], equal_link = measure(fol_params(prm0, axis=False, link=True))
+        equal = equal and equal_link
+        if a.axis:
+            out['axis_link'], equal_link = measure(fol_params(prm0, axis=True, link=True))
+            equal = equal and equal_link
     ctx.close()
     text = json.dumps(out)
     print(text)
