@@ -1,15 +1,18 @@
 // pdeval_fol_registry.hip -- the foliation class registry (DESIGN.md §14 "Registry"): the leaders'
-// gradient fields resident on the device across batches, fol_assign_kernel (Stage A: each row's
-// first match among them in one launch), fol_link_kernel (the link pass: every other leader a
-// row matches, "Links and components"), the store's append / export kernel and the
-// pdeval_fol_registry_* entry points.  Stage B and the fields reuse pdeval_foliation.hip.
+// gradient fields resident on the device across batches and the one pair scan over them,
+// fol_scan, in its two modes: Stage A (fol_assign_kernel: each row's first match, in one launch)
+// and the link pass (fol_link_kernel: every other leader a row matches, "Links and components");
+// the store's append / export kernel and the pdeval_fol_registry_* entry points.  Stage B and the
+// fields reuse pdeval_foliation.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pdeval.h"
@@ -18,7 +21,7 @@
 
 namespace pd {
 
-// Stage A.  One wave per row, four rows per 256-thread block; lanes are sample points.  The
+// The pair scan.  One wave per row, four rows per 256-thread block; lanes are sample points.  The
 // leaders are walked in creation order in tiles of T = kFolAssignTile: the block copies the
 // tile's first chunks (T x 1 KiB, contiguous in the chunk-major store) into LDS, the next tile
 // travelling in registers meanwhile, and each of its waves tests its row against them from
@@ -27,11 +30,28 @@ namespace pd {
 // reads the leader's later chunks, straight from global memory.  REG (m <= 16): the row's whole
 // field, at most 4 chunks x 2 doubles per lane, stays in registers for the scan; otherwise
 // only its first chunk does and the later ones are re-read per surviving pair.  Counts are
-// ballots into wave-uniform counters; a row is finished at its first match and a block when
-// its four rows are.  The only indices read are row < n_rows and leader < L, both loop bounds.
-// AXIS: the chunk test with the axis rule (PDEVAL_FOL_AXIS); AXIS = false is the kernel as it was.
-template <bool REG, bool AXIS>
-__global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
+// ballots into wave-uniform counters.  AXIS: the chunk test with the axis rule (PDEVAL_FOL_AXIS).
+// The mode supplies what differs, each under an `if constexpr (LINK)` below:
+//                     Stage A                              link pass
+//   the row scans     [0, L)                               [0, lim[row]) without cls[row]
+//   it scans nothing  n_finite[row] < min_points           cls[row] < 0
+//   the block walks   the tiles below L                    below the largest lim of its four rows
+//                                                          (one LDS word per wave and a barrier)
+//   on a match        first[row] = the leader, the row     lane 0 appends (cls[row], leader), the slot
+//                     is done                              taken by an atomic add on a device counter;
+//                                                          past ecap the edge is counted, not stored
+//                                                          (the host grows the buffer and repeats)
+//   the block ends    when its four rows are done          after its last tile
+// The only indices read are row < n_rows and leader < L (Stage A), leader < max lim <= L and
+// cls[row] in [-1, L) (link pass; the host checks lim and cls before the launch).  Edge order is
+// whatever the atomics give; the components do not depend on it.
+enum class FolMode { StageA, Link };
+template <FolMode MODE>
+using FolModeArgs = std::conditional_t<MODE == FolMode::Link, FolLinkArgs, FolAssignArgs>;
+
+template <FolMode MODE, bool REG, bool AXIS>
+__device__ __forceinline__ void fol_scan(const FolModeArgs<MODE>& a) {
+    constexpr bool LINK = MODE == FolMode::Link;
     constexpr int T = kFolAssignTile, NR = REG ? kFolRegChunks : 1;
     constexpr int kPf = T * 2 * kFolChunk / 2 / 256;   // double2 per thread and tile
     __shared__ double2 tile2[T * kFolChunk];
@@ -43,9 +63,18 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     const bool in_batch = row < a.n_rows;
     const double* ra = a.rows + (in_batch ? row : 0) * 2 * (int64_t)mm;
-    // (a row with fewer finite points than a match needs usable ones matches nothing)
+    // the row scans the leaders [0, lim) other than `own`; done: it scans nothing (more)
+    int64_t lim = a.L;
+    [[maybe_unused]] int own = -1;
     bool done = !in_batch;
-    if (in_batch && a.n_finite) done = __builtin_amdgcn_readfirstlane((int)(a.n_finite[row] < a.min_points)) != 0;
+    if constexpr (LINK) {
+        if (in_batch) own = __builtin_amdgcn_readfirstlane(a.cls[row]);
+        done = own < 0;
+        lim = done ? 0 : __builtin_amdgcn_readfirstlane(a.lim[row]);
+    } else {
+        // (a row with fewer finite points than a match needs usable ones matches nothing)
+        if (in_batch && a.n_finite) done = __builtin_amdgcn_readfirstlane((int)(a.n_finite[row] < a.min_points)) != 0;
+    }
     double fa[NR], fb[NR];
 #pragma unroll
     for (int c = 0; c < NR; ++c) {
@@ -54,10 +83,16 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
         fa[c] = p < mm ? ra[pc] : nan;
         fb[c] = p < mm ? ra[mm + pc] : nan;
     }
-    const int64_t L = a.L;
+    int64_t top = a.L;   // block-uniform: the leaders the block walks
+    if constexpr (LINK) {
+        __shared__ int s_lim[4];
+        if (lane == 0) s_lim[wib] = (int)lim;
+        __syncthreads();
+        top = max(max(s_lim[0], s_lim[1]), max(s_lim[2], s_lim[3]));   // <= L
+    }
     double2 pf[kPf];
     auto fetch = [&](int64_t t0) {
-        const int64_t n2 = (L - t0 < T ? L - t0 : T) * kFolChunk;   // double2 of the tile's leaders
+        const int n2 = (top - t0 < T ? (int)(top - t0) : T) * kFolChunk;   // double2 of the tile's leaders
         const double2* src = (const double2*)(a.store + fol_store_at(a.cap, 0, t0));
 #pragma unroll
         for (int i = 0; i < kPf; ++i) {
@@ -65,28 +100,30 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
             pf[i] = j < n2 ? src[j] : double2{nan, nan};
         }
     };
-    int64_t first = -1;
-    if (L > 0) fetch(0);
-    for (int64_t t0 = 0; t0 < L; t0 += T) {
+    [[maybe_unused]] int64_t first = -1;
+    if (top > 0) fetch(0);
+    for (int64_t t0 = 0; t0 < top; t0 += T) {
 #pragma unroll
         for (int i = 0; i < kPf; ++i) tile2[(int)threadIdx.x + 256 * i] = pf[i];
         __syncthreads();
-        if (t0 + T < L) fetch(t0 + T);
+        if (t0 + T < top) fetch(t0 + T);
         if (!done) {
-            const int tn = L - t0 < T ? (int)(L - t0) : T;
+            const int tn = lim - t0 < T ? (int)(lim - t0) : T;   // (<= 0 for a row whose leaders end before this tile)
             for (int k = 0; k < tn; ++k) {
+                const int64_t l = t0 + k;
+                if constexpr (LINK)
+                    if (l == own) continue;
                 const double* q0 = tile + k * 2 * kFolChunk;
                 FolCount n{0, 0};
                 fol_chunk_test<AXIS>(fa[0], fb[0], q0[lane], q0[kFolChunk + lane], lane < mm, a.tau, n);
                 if (n.nb) continue;
-                const int64_t l = t0 + k;
                 if constexpr (REG) {
 #pragma unroll
                     for (int c = 1; c < NR; ++c)
                         if (c < a.n_chunk && !n.nb) {
                             const double* q = a.store + fol_store_at(a.cap, c, l);
                             fol_chunk_test<AXIS>(fa[c], fb[c], q[lane], q[kFolChunk + lane], c * kFolChunk + lane < mm,
-                                           a.tau, n);
+                                                 a.tau, n);
                         }
                 } else {
                     for (int c = 1; c < a.n_chunk && !n.nb; ++c) {
@@ -97,123 +134,54 @@ __global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
                     }
                 }
                 if (n.nu >= a.min_points && n.nb == 0) {
-                    first = l;
-                    done = true;
-                    break;
+                    if constexpr (LINK) {
+                        if (lane == 0) {
+                            const unsigned long long slot = atomicAdd(a.count, 1ull);
+                            if (slot < (unsigned long long)a.ecap) {
+                                a.edges[2 * slot] = own;
+                                a.edges[2 * slot + 1] = (int32_t)l;
+                            }
+                        }
+                    } else {
+                        first = l;
+                        done = true;
+                        break;
+                    }
                 }
             }
         }
-        // (also the barrier between this tile's readers and the next tile's writers)
-        if (__syncthreads_and(done)) break;
+        // (every exit is also the barrier between this tile's readers and the next tile's writers)
+        if constexpr (LINK) __syncthreads();
+        else if (__syncthreads_and(done)) break;
     }
-    if (lane == 0 && in_batch) a.first[row] = first;
+    if constexpr (!LINK)
+        if (lane == 0 && in_batch) a.first[row] = first;
 }
 
-void launch_fol_assign(const FolAssignArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.n_rows + 3) / 4)), block(256);
-    const bool reg = a.n_chunk <= kFolRegChunks, axis = (a.flags & PDEVAL_FOL_AXIS) != 0;
-    if (reg && !axis) hipLaunchKernelGGL((fol_assign_kernel<true, false>), grid, block, 0, s, a);
-    else if (!reg && !axis) hipLaunchKernelGGL((fol_assign_kernel<false, false>), grid, block, 0, s, a);
-    else if (reg) hipLaunchKernelGGL((fol_assign_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((fol_assign_kernel<false, true>), grid, block, 0, s, a);
+template <bool REG, bool AXIS>
+__global__ __launch_bounds__(256) void fol_assign_kernel(FolAssignArgs a) {
+    fol_scan<FolMode::StageA, REG, AXIS>(a);
 }
-
-// The link pass (DESIGN.md §14 "Links and components").  The shape of Stage A -- one wave per
-// row, four rows per block, the leaders' first chunks in LDS tiles of T, REG at m <= 16, a pair
-// left at its first bad chunk -- with these differences: a row does not stop at a match, it scans
-// the leaders [0, lim[row]) and skips its own class cls[row], and for every match lane 0 appends
-// the pair (cls[row], leader) to the edge buffer, the slot taken by an atomic add on a device
-// counter; an edge past the buffer's capacity is counted and not stored (the host grows the
-// buffer and repeats the launch).  A row with cls[row] < 0 scans nothing.  The block walks the
-// tiles below the largest lim of its four rows, so the only indices read are row < n_rows and
-// leader < max lim <= L; the host checks lim and cls before the launch.  Edge order is
-// whatever the atomics give; the components do not depend on it.
 template <bool REG, bool AXIS>
 __global__ __launch_bounds__(256) void fol_link_kernel(FolLinkArgs a) {
-    constexpr int T = kFolAssignTile, NR = REG ? kFolRegChunks : 1;
-    constexpr int kPf = T * 2 * kFolChunk / 2 / 256;   // double2 per thread and tile
-    __shared__ double2 tile2[T * kFolChunk];
-    __shared__ int s_lim[4];
-    const double* tile = (const double*)tile2;
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t row = (int64_t)blockIdx.x * 4 + wib;
-    const int mm = a.mm;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    const bool in_batch = row < a.n_rows;
-    const double* ra = a.rows + (in_batch ? row : 0) * 2 * (int64_t)mm;
-    const int own = in_batch ? __builtin_amdgcn_readfirstlane(a.cls[row]) : -1;
-    const int lim = own >= 0 ? __builtin_amdgcn_readfirstlane(a.lim[row]) : 0;
-    if (lane == 0) s_lim[wib] = lim;
-    double fa[NR], fb[NR];
-#pragma unroll
-    for (int c = 0; c < NR; ++c) {
-        const int p = c * kFolChunk + lane;
-        const int pc = p < mm ? p : mm - 1;
-        fa[c] = p < mm ? ra[pc] : nan;
-        fb[c] = p < mm ? ra[mm + pc] : nan;
-    }
-    __syncthreads();
-    const int top = max(max(s_lim[0], s_lim[1]), max(s_lim[2], s_lim[3]));   // block-uniform, <= L
-    double2 pf[kPf];
-    auto fetch = [&](int t0) {
-        const int n2 = (top - t0 < T ? top - t0 : T) * kFolChunk;   // double2 of the tile's leaders
-        const double2* src = (const double2*)(a.store + fol_store_at(a.cap, 0, t0));
-#pragma unroll
-        for (int i = 0; i < kPf; ++i) {
-            const int j = (int)threadIdx.x + 256 * i;
-            pf[i] = j < n2 ? src[j] : double2{nan, nan};
-        }
-    };
-    if (top > 0) fetch(0);
-    for (int t0 = 0; t0 < top; t0 += T) {
-#pragma unroll
-        for (int i = 0; i < kPf; ++i) tile2[(int)threadIdx.x + 256 * i] = pf[i];
-        __syncthreads();
-        if (t0 + T < top) fetch(t0 + T);
-        const int tn = lim - t0 < T ? lim - t0 : T;   // (<= 0 for a row whose leaders end before this tile)
-        for (int k = 0; k < tn; ++k) {
-            const int l = t0 + k;
-            if (l == own) continue;
-            const double* q0 = tile + k * 2 * kFolChunk;
-            FolCount n{0, 0};
-            fol_chunk_test<AXIS>(fa[0], fb[0], q0[lane], q0[kFolChunk + lane], lane < mm, a.tau, n);
-            if (n.nb) continue;
-            if constexpr (REG) {
-#pragma unroll
-                for (int c = 1; c < NR; ++c)
-                    if (c < a.n_chunk && !n.nb) {
-                        const double* q = a.store + fol_store_at(a.cap, c, l);
-                        fol_chunk_test<AXIS>(fa[c], fb[c], q[lane], q[kFolChunk + lane], c * kFolChunk + lane < mm,
-                                             a.tau, n);
-                    }
-            } else {
-                for (int c = 1; c < a.n_chunk && !n.nb; ++c) {
-                    const double* q = a.store + fol_store_at(a.cap, c, l);
-                    const int p = c * kFolChunk + lane;
-                    const int pc = p < mm ? p : mm - 1;
-                    fol_chunk_test<AXIS>(ra[pc], ra[mm + pc], q[lane], q[kFolChunk + lane], p < mm, a.tau, n);
-                }
-            }
-            if (n.nu >= a.min_points && n.nb == 0 && lane == 0) {
-                const unsigned long long slot = atomicAdd(a.count, 1ull);
-                if (slot < (unsigned long long)a.ecap) {
-                    a.edges[2 * slot] = own;
-                    a.edges[2 * slot + 1] = l;
-                }
-            }
-        }
-        __syncthreads();   // this tile's readers before the next tile's writers
-    }
+    fol_scan<FolMode::Link, REG, AXIS>(a);
 }
 
+// launches k[REG + 2 AXIS], the instantiation the arguments select
+template <class Args>
+void launch_fol_scan(void (*const (&k)[4])(Args), const Args& a, hipStream_t s) {
+    const int v = (a.n_chunk <= kFolRegChunks ? 1 : 0) + ((a.flags & PDEVAL_FOL_AXIS) ? 2 : 0);
+    hipLaunchKernelGGL(k[v], dim3((unsigned)((a.n_rows + 3) / 4)), dim3(256), 0, s, a);
+}
+void launch_fol_assign(const FolAssignArgs& a, hipStream_t s) {
+    static void (*const k[4])(FolAssignArgs) = {fol_assign_kernel<false, false>, fol_assign_kernel<true, false>,
+                                                fol_assign_kernel<false, true>, fol_assign_kernel<true, true>};
+    launch_fol_scan(k, a, s);
+}
 void launch_fol_link(const FolLinkArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.n_rows + 3) / 4)), block(256);
-    const bool reg = a.n_chunk <= kFolRegChunks, axis = (a.flags & PDEVAL_FOL_AXIS) != 0;
-    if (reg && !axis) hipLaunchKernelGGL((fol_link_kernel<true, false>), grid, block, 0, s, a);
-    else if (!reg && !axis) hipLaunchKernelGGL((fol_link_kernel<false, false>), grid, block, 0, s, a);
-    else if (reg) hipLaunchKernelGGL((fol_link_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((fol_link_kernel<false, true>), grid, block, 0, s, a);
+    static void (*const k[4])(FolLinkArgs) = {fol_link_kernel<false, false>, fol_link_kernel<true, false>,
+                                              fol_link_kernel<false, true>, fol_link_kernel<true, true>};
+    launch_fol_scan(k, a, s);
 }
 
 // One wave per (leader, chunk) of the call.  to_store: leader k's field, fields[idx[k]] (or
@@ -271,119 +239,99 @@ void launch_fol_nfinite(const double* fields, int64_t n_rows, int mm, int32_t* n
 
 using namespace pd;
 
+// The four timing events of a registry: all of them or none.
+struct FolEvents {
+    hipEvent_t e[4] = {};
+    FolEvents() = default;
+    FolEvents(const FolEvents&) = delete;
+    FolEvents& operator=(const FolEvents&) = delete;
+    ~FolEvents() { clear(); }
+    void clear() {
+        for (hipEvent_t& x : e) {
+            if (x) (void)hipEventDestroy(x);
+            x = nullptr;
+        }
+    }
+    hipError_t create() {
+        for (hipEvent_t& x : e) {
+            const hipError_t err = hipEventCreate(&x);
+            if (err != hipSuccess) {
+                x = nullptr;
+                clear();
+                return err;
+            }
+        }
+        return hipSuccess;
+    }
+};
+
 // A registry: bound to one context and one parameter set.  The leader store and the scratch of
-// a batch belong to it and are reused between calls.
+// a batch belong to it and are reused between calls; each buffer knows its own capacity.
 struct pdeval_fol_registry {
     pdeval_ctx* ctx = nullptr;
     FolCtx v{};
     pdeval_fol_params prm{};
     int mm = 0, n_chunk = 0;
-    double* d_store = nullptr;   // chunk-major, cap leaders (fol_store_at)
-    int64_t cap = 0;
+    DevBuf<double> d_store;   // chunk-major, cap() leaders (fol_store_at)
     FolBook book;
-    // scratch of a batch, batch_cap rows: Stage A's first[], the finite counts, Stage B's indices and masks
-    int64_t batch_cap = 0;
-    int64_t* d_first = nullptr;
-    int32_t* d_nfin = nullptr;
-    int64_t* d_idx = nullptr;
-    uint32_t* d_mask = nullptr;
-    // the fields of a batch of programs, field_cap rows (pdeval_fol_registry_assign)
-    int64_t field_cap = 0;
-    double* d_field = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;   // around Stage A's launch
+    // scratch of a batch: Stage A's first[], the finite counts, Stage B's indices and masks
+    DevBuf<int64_t> d_first, d_idx;
+    DevBuf<int32_t> d_nfin;
+    DevBuf<uint32_t> d_mask;
+    DevBuf<double> d_field;   // the fields of a batch of programs (pdeval_fol_registry_assign)
+    FolEvents ev;             // e[0], e[1] around Stage A's launch; e[2], e[3] around each launch of the link kernel
     bool timed = false;
     // the link pass (PDEVAL_FOL_LINK, pdeval_fol_registry_link_fields): the rows' classes and scan
-    // limits, link_cap rows; the edge buffer, edge_cap pairs, and its counter; allocated at first use
-    int64_t link_cap = 0, edge_cap = 0, edge_hint = 0;
-    int32_t* d_cls = nullptr;
-    int32_t* d_lim = nullptr;
-    int32_t* d_edges = nullptr;
-    unsigned long long* d_count = nullptr;
-    hipEvent_t e2 = nullptr, e3 = nullptr;   // around each launch of the link kernel
-    double link_ms = 0.0;                    // their sum over the most recent call
+    // limits, the edge buffer (edge_cap() pairs) and its counter; allocated at first use
+    int64_t edge_hint = 0;
+    DevBuf<int32_t> d_cls, d_lim, d_edges;
+    DevBuf<unsigned long long> d_count;
+    double link_ms = 0.0;     // the link kernel's launches of the most recent call, summed
     std::vector<int32_t> cls32, lim32, edges;
     std::vector<FolBook::Link> merged, fresh;
     // host buffers of a batch, reused
     std::vector<int64_t> first, leader_b, un, new_rows, ids;
     std::vector<int32_t> nfin;
+
+    int64_t leader_doubles() const { return (int64_t)n_chunk * 2 * kFolChunk; }
+    int64_t cap() const { return d_store.cap / leader_doubles(); }
+    int64_t edge_cap() const { return d_edges.cap / 2; }
 };
 
 namespace {
-size_t store_bytes(const pdeval_fol_registry* r, int64_t cap) {
-    return (size_t)cap * (size_t)r->n_chunk * 2 * kFolChunk * sizeof(double);
-}
-
 // the store holds `need` leaders: doubling, outside any kernel (new allocation, one
 // device-to-device copy per chunk plane, free); on failure nothing has changed
 int reg_reserve(pdeval_fol_registry* r, int64_t need) {
-    if (need <= r->cap) return PDEVAL_OK;
-    const int64_t cap = fol_next_capacity(r->cap, need);
-    double* d_new = nullptr;
-    if (hipMalloc((void**)&d_new, store_bytes(r, cap)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (need <= r->cap()) return PDEVAL_OK;
+    const int64_t cap = fol_next_capacity(r->cap(), need);
+    DevBuf<double> grown;
+    if (!grown.reserve(cap * r->leader_doubles()))
         return fol_fail(r->ctx, PDEVAL_ERR_ALLOC,
-                        ("pdeval_fol_registry: cannot allocate " + std::to_string(store_bytes(r, cap)) +
+                        ("pdeval_fol_registry: cannot allocate " +
+                         std::to_string((size_t)cap * (size_t)r->leader_doubles() * sizeof(double)) +
                          " bytes of leader fields (capacity x chunks x 1 KiB)").c_str());
-    }
     const int64_t L = r->book.n_classes();
     hipError_t e = hipSuccess;
     for (int c = 0; c < r->n_chunk && L > 0 && e == hipSuccess; ++c)
-        e = hipMemcpyAsync(d_new + fol_store_at(cap, c, 0), r->d_store + fol_store_at(r->cap, c, 0),
+        e = hipMemcpyAsync(grown.p + fol_store_at(cap, c, 0), r->d_store.p + fol_store_at(r->cap(), c, 0),
                            (size_t)L * 2 * kFolChunk * sizeof(double), hipMemcpyDeviceToDevice, r->v.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->v.stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_new);
-        return fol_hip_fail(r->ctx, "hipMemcpyAsync", e);
-    }
-    (void)hipFree(r->d_store);
-    r->d_store = d_new;
-    r->cap = cap;
+    if (e != hipSuccess) return fol_hip_fail(r->ctx, "hipMemcpyAsync", e);
+    r->d_store.swap(grown);
     return PDEVAL_OK;
 }
 
-// the scratch of a batch of n rows (and, with_field, its fields): hipMalloc only when a batch
-// outgrows what is there
+// the scratch of a batch of n rows (and, with_field, its fields): a buffer is reallocated only
+// when a batch outgrows it
 int reg_scratch(pdeval_fol_registry* r, int64_t n, bool with_field) {
-    if (n > r->batch_cap) {
-        int64_t* d_first = nullptr;
-        int32_t* d_nfin = nullptr;
-        int64_t* d_idx = nullptr;
-        uint32_t* d_mask = nullptr;
-        if (hipMalloc((void**)&d_first, (size_t)n * sizeof(int64_t)) != hipSuccess ||
-            hipMalloc((void**)&d_nfin, (size_t)n * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void**)&d_idx, (size_t)n * sizeof(int64_t)) != hipSuccess ||
-            hipMalloc((void**)&d_mask, (size_t)n * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(d_first);
-            (void)hipFree(d_nfin);
-            (void)hipFree(d_idx);
-            (void)hipFree(d_mask);
-            return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the batch buffers");
-        }
-        (void)hipFree(r->d_first);
-        (void)hipFree(r->d_nfin);
-        (void)hipFree(r->d_idx);
-        (void)hipFree(r->d_mask);
-        r->d_first = d_first;
-        r->d_nfin = d_nfin;
-        r->d_idx = d_idx;
-        r->d_mask = d_mask;
-        r->batch_cap = n;
-    }
-    if (with_field && n > r->field_cap) {
-        double* d_field = nullptr;
-        const size_t bytes = (size_t)n * 2 * (size_t)r->mm * sizeof(double);
-        if (hipMalloc((void**)&d_field, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fol_fail(r->ctx, PDEVAL_ERR_ALLOC,
-                            ("pdeval_fol_registry_assign: cannot allocate " + std::to_string(bytes) +
-                             " bytes of gradient fields (n_list x 2 m^2 x 8): assign a shorter list or a smaller m")
-                                .c_str());
-        }
-        (void)hipFree(r->d_field);
-        r->d_field = d_field;
-        r->field_cap = n;
-    }
+    if (!r->d_first.reserve(n) || !r->d_nfin.reserve(n) || !r->d_idx.reserve(n) || !r->d_mask.reserve(n))
+        return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the batch buffers");
+    const int64_t doubles = n * 2 * (int64_t)r->mm;
+    if (with_field && !r->d_field.reserve(doubles))
+        return fol_fail(r->ctx, PDEVAL_ERR_ALLOC,
+                        ("pdeval_fol_registry_assign: cannot allocate " + std::to_string((size_t)doubles * sizeof(double)) +
+                         " bytes of gradient fields (n_list x 2 m^2 x 8): assign a shorter list or a smaller m")
+                            .c_str());
     return PDEVAL_OK;
 }
 
@@ -397,46 +345,35 @@ int reg_check(pdeval_ctx* c, pdeval_fol_registry* r, const char* fn) {
     return PDEVAL_OK;
 }
 
-void reg_move_args(const pdeval_fol_registry* r, FolMoveArgs* a) {
-    a->store = r->d_store;
-    a->cap = r->cap;
-    a->mm = r->mm;
-    a->n_chunk = r->n_chunk;
+// what both modes of the scan take: the rows d_fields against the store's leaders [0, L)
+FolScanArgs reg_scan_args(const pdeval_fol_registry* r, const double* d_fields, int64_t n, int64_t L) {
+    return {d_fields, n, r->d_store.p, r->cap(), L, r->mm, r->n_chunk, r->prm.tau, r->prm.min_points,
+            (uint32_t)r->prm.flags};
+}
+
+// fol_move_kernel between the store's leaders base .. base + n_lead - 1 and `fields` (n_rows rows,
+// leader k's at idx[k], or at k without idx), waited for
+int reg_move(pdeval_fol_registry* r, int64_t base, int64_t n_lead, double* fields, int64_t n_rows, const int64_t* idx,
+             bool to_store) {
+    const FolMoveArgs m{r->d_store.p, r->cap(), base, n_lead, fields, n_rows, idx, r->mm, r->n_chunk, to_store ? 1 : 0};
+    launch_fol_move(m, r->v.stream);
+    hipError_t e;
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(r->v.stream)) != hipSuccess)
+        return fol_hip_fail(r->ctx, "fol_move_kernel", e);
+    return PDEVAL_OK;
 }
 
 // the buffers of a link pass over n rows; the edge buffer holds at least `edges` pairs
 int reg_link_scratch(pdeval_fol_registry* r, int64_t n, int64_t edges) {
-    if (n > r->link_cap) {
-        int32_t* d_cls = nullptr;
-        int32_t* d_lim = nullptr;
-        if (hipMalloc((void**)&d_cls, (size_t)n * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc((void**)&d_lim, (size_t)n * sizeof(int32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(d_cls);
-            return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the link pass's row buffers");
-        }
-        (void)hipFree(r->d_cls);
-        (void)hipFree(r->d_lim);
-        r->d_cls = d_cls;
-        r->d_lim = d_lim;
-        r->link_cap = n;
-    }
-    if (!r->d_count && hipMalloc((void**)&r->d_count, sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipGetLastError();
-        r->d_count = nullptr;
+    if (!r->d_cls.reserve(n) || !r->d_lim.reserve(n))
+        return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the link pass's row buffers");
+    if (!r->d_count.reserve(1))
         return fol_fail(r->ctx, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the edge counter");
-    }
-    if (edges > r->edge_cap) {
-        const int64_t cap = fol_next_capacity(r->edge_cap, edges);
-        int32_t* d_edges = nullptr;
-        if (hipMalloc((void**)&d_edges, (size_t)cap * 2 * sizeof(int32_t)) != hipSuccess) {
-            (void)hipGetLastError();
+    if (edges > r->edge_cap()) {
+        const int64_t cap = fol_next_capacity(r->edge_cap(), edges);
+        if (!r->d_edges.reserve(2 * cap))
             return fol_fail(r->ctx, PDEVAL_ERR_ALLOC,
                             ("pdeval_fol_registry: cannot allocate an edge buffer of " + std::to_string(cap) + " pairs").c_str());
-        }
-        (void)hipFree(r->d_edges);
-        r->d_edges = d_edges;
-        r->edge_cap = cap;
     }
     return PDEVAL_OK;
 }
@@ -457,44 +394,30 @@ int reg_link(pdeval_fol_registry* r, const double* d_fields, int64_t n, int64_t 
         int rc = reg_link_scratch(r, n, std::max<int64_t>(r->edge_hint, 1));
         if (rc != PDEVAL_OK) return rc;
         hipError_t e;
-        if ((e = hipMemcpyAsync(r->d_cls, r->cls32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess ||
-            (e = hipMemcpyAsync(r->d_lim, r->lim32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess)
+        if ((e = hipMemcpyAsync(r->d_cls.p, r->cls32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess ||
+            (e = hipMemcpyAsync(r->d_lim.p, r->lim32.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s)) != hipSuccess)
             return fol_hip_fail(c, "hipMemcpyAsync", e);
         // at most two launches: the second with a buffer that holds what the first counted
         for (int pass = 0; pass < 2; ++pass) {
-            FolLinkArgs a{};
-            a.rows = d_fields;
-            a.n_rows = n;
-            a.cls = r->d_cls;
-            a.lim = r->d_lim;
-            a.store = r->d_store;
-            a.cap = r->cap;
-            a.L = L;
-            a.mm = r->mm;
-            a.n_chunk = r->n_chunk;
-            a.tau = r->prm.tau;
-            a.min_points = r->prm.min_points;
-            a.edges = r->d_edges;
-            a.ecap = r->edge_cap;
-            a.count = r->d_count;
-            a.flags = (uint32_t)r->prm.flags;
-            if ((e = hipMemsetAsync(r->d_count, 0, sizeof(unsigned long long), s)) != hipSuccess)
+            const FolLinkArgs a{reg_scan_args(r, d_fields, n, L), r->d_cls.p, r->d_lim.p, r->d_edges.p, r->edge_cap(),
+                                r->d_count.p};
+            if ((e = hipMemsetAsync(r->d_count.p, 0, sizeof(unsigned long long), s)) != hipSuccess)
                 return fol_hip_fail(c, "hipMemsetAsync", e);
-            (void)hipEventRecord(r->e2, s);
+            (void)hipEventRecord(r->ev.e[2], s);
             launch_fol_link(a, s);
             if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_link_kernel", e);
-            (void)hipEventRecord(r->e3, s);
+            (void)hipEventRecord(r->ev.e[3], s);
             unsigned long long count = 0;
-            if ((e = hipMemcpyAsync(&count, r->d_count, sizeof(count), hipMemcpyDeviceToHost, s)) != hipSuccess)
+            if ((e = hipMemcpyAsync(&count, r->d_count.p, sizeof(count), hipMemcpyDeviceToHost, s)) != hipSuccess)
                 return fol_hip_fail(c, "hipMemcpyAsync", e);
             if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "fol_link_kernel", e);
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, r->e2, r->e3) != hipSuccess) (void)hipGetLastError();
+            if (hipEventElapsedTime(&ms, r->ev.e[2], r->ev.e[3]) != hipSuccess) (void)hipGetLastError();
             else r->link_ms += ms;
             // (a row yields at most one edge per leader other than its own)
             if (count > (unsigned long long)n * (unsigned long long)(L - 1))
                 return fol_fail(c, PDEVAL_ERR_HIP, "pdeval_fol_registry: fol_link_kernel counted more edges than pairs");
-            if ((int64_t)count > r->edge_cap) {
+            if ((int64_t)count > r->edge_cap()) {
                 if (pass == 1)
                     return fol_fail(c, PDEVAL_ERR_HIP, "pdeval_fol_registry: fol_link_kernel counted more edges the second time");
                 if ((rc = reg_link_scratch(r, n, (int64_t)count)) != PDEVAL_OK) return rc;
@@ -506,7 +429,7 @@ int reg_link(pdeval_fol_registry* r, const double* d_fields, int64_t n, int64_t 
                 return fol_fail(c, PDEVAL_ERR_ALLOC, "pdeval_fol_registry: cannot allocate the host copy of the edges");
             }
             if (count > 0) {
-                if ((e = hipMemcpyAsync(r->edges.data(), r->d_edges, (size_t)count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+                if ((e = hipMemcpyAsync(r->edges.data(), r->d_edges.p, (size_t)count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
                     return fol_hip_fail(c, "hipMemcpyAsync", e);
                 if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "hipMemcpyAsync", e);
             }
@@ -545,25 +468,13 @@ int reg_assign(pdeval_fol_registry* r, const double* d_fields, const int32_t* d_
     r->nfin.resize((size_t)n);
     r->timed = false;
     if (L > 0) {   // Stage A: one launch and one download whatever L is
-        FolAssignArgs a{};
-        a.rows = d_fields;
-        a.n_rows = n;
-        a.n_finite = d_nfin;
-        a.store = r->d_store;
-        a.cap = r->cap;
-        a.L = L;
-        a.mm = r->mm;
-        a.n_chunk = r->n_chunk;
-        a.tau = r->prm.tau;
-        a.min_points = r->prm.min_points;
-        a.first = r->d_first;
-        a.flags = (uint32_t)r->prm.flags;
-        (void)hipEventRecord(r->e0, s);
+        const FolAssignArgs a{reg_scan_args(r, d_fields, n, L), d_nfin, r->d_first.p};
+        (void)hipEventRecord(r->ev.e[0], s);
         launch_fol_assign(a, s);
         if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_assign_kernel", e);
-        (void)hipEventRecord(r->e1, s);
+        (void)hipEventRecord(r->ev.e[1], s);
         r->timed = true;
-        if ((e = hipMemcpyAsync(r->first.data(), r->d_first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+        if ((e = hipMemcpyAsync(r->first.data(), r->d_first.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
             return fol_hip_fail(c, "hipMemcpyAsync", e);
     }
     if ((e = hipMemcpyAsync(r->nfin.data(), d_nfin, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
@@ -576,7 +487,7 @@ int reg_assign(pdeval_fol_registry* r, const double* d_fields, const int32_t* d_
     r->leader_b.assign((size_t)n, -1);
     int64_t classes = 0;
     int32_t rounds = 0;
-    int rc = fol_rounds(c, d_fields, r->mm, r->prm, r->un, nullptr, r->leader_b.data(), r->d_idx, r->d_mask, s,
+    int rc = fol_rounds(c, d_fields, r->mm, r->prm, r->un, nullptr, r->leader_b.data(), r->d_idx.p, r->d_mask.p, s,
                         &classes, &rounds);
     if (rc != PDEVAL_OK) return rc;
     r->ids.resize((size_t)n);
@@ -586,19 +497,9 @@ int reg_assign(pdeval_fol_registry* r, const double* d_fields, const int32_t* d_
     // the append: room first (a failure leaves the registry as it was), then the new leaders' fields
     if (classes > 0) {
         if ((rc = reg_reserve(r, L + classes)) != PDEVAL_OK) return rc;
-        if ((e = hipMemcpyAsync(r->d_idx, r->new_rows.data(), (size_t)classes * sizeof(int64_t), hipMemcpyHostToDevice, s)) != hipSuccess)
+        if ((e = hipMemcpyAsync(r->d_idx.p, r->new_rows.data(), (size_t)classes * sizeof(int64_t), hipMemcpyHostToDevice, s)) != hipSuccess)
             return fol_hip_fail(c, "hipMemcpyAsync", e);
-        FolMoveArgs m{};
-        reg_move_args(r, &m);
-        m.base = L;
-        m.n_lead = classes;
-        m.fields = const_cast<double*>(d_fields);
-        m.n_rows = n;
-        m.idx = r->d_idx;
-        m.to_store = 1;
-        launch_fol_move(m, s);
-        if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
-        if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
+        if ((rc = reg_move(r, L, classes, const_cast<double*>(d_fields), n, r->d_idx.p, true)) != PDEVAL_OK) return rc;
     }
     // the link pass (PDEVAL_FOL_LINK): the batch's rows, by the arrival rule, against the store as
     // the batch leaves it; planned before the commit, committed with it
@@ -625,51 +526,23 @@ extern "C" int pdeval_fol_registry_create(pdeval_ctx* c, const pdeval_fol_params
         return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry_create: bad argument");
     hipError_t e = hipSetDevice(v.device);
     if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
-    pdeval_fol_registry* r = new pdeval_fol_registry;
+    std::unique_ptr<pdeval_fol_registry> r(new pdeval_fol_registry);   // (a failure below frees what it holds)
     r->ctx = c;
     r->v = v;
     r->prm = prm;
     r->mm = prm.m * prm.m;
     r->n_chunk = (r->mm + kFolChunk - 1) / kFolChunk;
     r->edge_hint = std::max<int64_t>(capacity_hint, kFolEdgeMin);
-    if ((e = hipEventCreate(&r->e0)) != hipSuccess || (e = hipEventCreate(&r->e1)) != hipSuccess ||
-        (e = hipEventCreate(&r->e2)) != hipSuccess || (e = hipEventCreate(&r->e3)) != hipSuccess) {
-        if (r->e0) (void)hipEventDestroy(r->e0);
-        if (r->e1) (void)hipEventDestroy(r->e1);
-        if (r->e2) (void)hipEventDestroy(r->e2);
-        delete r;
-        return fol_hip_fail(c, "hipEventCreate", e);
-    }
-    if ((rc = reg_reserve(r, std::max<int64_t>(capacity_hint, 1))) != PDEVAL_OK) {
-        (void)hipEventDestroy(r->e0);
-        (void)hipEventDestroy(r->e1);
-        (void)hipEventDestroy(r->e2);
-        (void)hipEventDestroy(r->e3);
-        delete r;
-        return rc;
-    }
-    *out = r;
+    if ((e = r->ev.create()) != hipSuccess) return fol_hip_fail(c, "hipEventCreate", e);
+    if ((rc = reg_reserve(r.get(), std::max<int64_t>(capacity_hint, 1))) != PDEVAL_OK) return rc;
+    *out = r.release();
     return PDEVAL_OK;
 }
 
 extern "C" int pdeval_fol_registry_destroy(pdeval_fol_registry* r) {
     if (!r) return PDEVAL_OK;
     (void)hipSetDevice(r->v.device);
-    (void)hipFree(r->d_store);
-    (void)hipFree(r->d_first);
-    (void)hipFree(r->d_nfin);
-    (void)hipFree(r->d_idx);
-    (void)hipFree(r->d_mask);
-    (void)hipFree(r->d_field);
-    (void)hipFree(r->d_cls);
-    (void)hipFree(r->d_lim);
-    (void)hipFree(r->d_edges);
-    (void)hipFree(r->d_count);
-    (void)hipEventDestroy(r->e0);
-    (void)hipEventDestroy(r->e1);
-    (void)hipEventDestroy(r->e2);
-    (void)hipEventDestroy(r->e3);
-    delete r;
+    delete r;   // its buffers and events with it
     return PDEVAL_OK;
 }
 
@@ -686,9 +559,9 @@ extern "C" int pdeval_fol_registry_assign_fields(pdeval_ctx* c, pdeval_fol_regis
     if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
     if ((rc = reg_scratch(r, n_rows, false)) != PDEVAL_OK) return rc;
     if (!d_n_finite) {
-        launch_fol_nfinite(d_fields, n_rows, r->mm, r->d_nfin, r->v.stream);
+        launch_fol_nfinite(d_fields, n_rows, r->mm, r->d_nfin.p, r->v.stream);
         if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_nfinite_kernel", e);
-        d_n_finite = r->d_nfin;
+        d_n_finite = r->d_nfin.p;
     }
     return reg_assign(r, d_fields, d_n_finite, n_rows, keys, class_id, n_new);
 }
@@ -708,10 +581,10 @@ extern "C" int pdeval_fol_registry_assign(pdeval_ctx* c, pdeval_fol_registry* r,
     hipError_t e = hipSetDevice(r->v.device);
     if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
     if ((rc = reg_scratch(r, n_list, true)) != PDEVAL_OK) return rc;
-    rc = fol_fields_launch(c, r->v, r->prm, d_ops, n_words, d_offsets, n, d_list, n_list, r->d_field, r->d_nfin,
+    rc = fol_fields_launch(c, r->v, r->prm, d_ops, n_words, d_offsets, n, d_list, n_list, r->d_field.p, r->d_nfin.p,
                            r->v.stream);
     if (rc != PDEVAL_OK) return rc;
-    return reg_assign(r, r->d_field, r->d_nfin, n_list, keys, class_id, n_new);
+    return reg_assign(r, r->d_field.p, r->d_nfin.p, n_list, keys, class_id, n_new);
 }
 
 extern "C" int pdeval_fol_registry_size(pdeval_fol_registry* r, int64_t* n_classes, int64_t* n_rows_seen) {
@@ -728,7 +601,7 @@ extern "C" int pdeval_fol_registry_info(pdeval_fol_registry* r, pdeval_fol_param
     if (grid) std::copy(r->v.grid, r->v.grid + 8, grid);
     if (stage_a_ms) {
         float ms = 0.f;
-        if (r->timed && hipEventElapsedTime(&ms, r->e0, r->e1) != hipSuccess) {
+        if (r->timed && hipEventElapsedTime(&ms, r->ev.e[0], r->ev.e[1]) != hipSuccess) {
             (void)hipGetLastError();
             ms = 0.f;
         }
@@ -740,24 +613,13 @@ extern "C" int pdeval_fol_registry_info(pdeval_fol_registry* r, pdeval_fol_param
 extern "C" int pdeval_fol_registry_leaders(pdeval_fol_registry* r, double* d_fields, int64_t* leader_keys,
                                            int64_t* sizes) {
     if (!r) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_fol_registry_leaders: null registry");
-    pdeval_ctx* c = r->ctx;
     const int64_t L = r->book.n_classes();
     if (leader_keys) std::copy(r->book.keys.begin(), r->book.keys.end(), leader_keys);
     if (sizes) std::copy(r->book.sizes.begin(), r->book.sizes.end(), sizes);
     if (!d_fields || L == 0) return PDEVAL_OK;
     hipError_t e = hipSetDevice(r->v.device);
-    if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
-    FolMoveArgs m{};
-    reg_move_args(r, &m);
-    m.base = 0;
-    m.n_lead = L;
-    m.fields = d_fields;
-    m.n_rows = L;
-    m.to_store = 0;
-    launch_fol_move(m, r->v.stream);
-    if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
-    if ((e = hipStreamSynchronize(r->v.stream)) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
-    return PDEVAL_OK;
+    if (e != hipSuccess) return fol_hip_fail(r->ctx, "hipSetDevice", e);
+    return reg_move(r, 0, L, d_fields, L, nullptr, false);
 }
 
 extern "C" int pdeval_fol_registry_kinds(pdeval_fol_registry* r, uint8_t* kinds) {
@@ -768,24 +630,21 @@ extern "C" int pdeval_fol_registry_kinds(pdeval_fol_registry* r, uint8_t* kinds)
     if (!kinds) return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_fol_registry_kinds: bad argument");
     hipError_t e = hipSetDevice(r->v.device);
     if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
-    uint8_t* d_kind = nullptr;
-    if (hipMalloc((void**)&d_kind, (size_t)L) != hipSuccess) {
-        (void)hipGetLastError();
+    DevBuf<uint8_t> d_kind;
+    if (!d_kind.reserve(L))
         return fol_fail(c, PDEVAL_ERR_ALLOC, "pdeval_fol_registry_kinds: cannot allocate the kinds");
-    }
     FolKindArgs a{};
-    a.fields = r->d_store;   // the leaders where they are: chunk-major (fol_store_at)
+    a.fields = r->d_store.p;   // the leaders where they are: chunk-major (fol_store_at)
     a.n_rows = L;
-    a.cap = r->cap;
+    a.cap = r->cap();
     a.mm = r->mm;
     a.n_chunk = r->n_chunk;
     a.min_points = r->prm.min_points;
-    a.kind = d_kind;
+    a.kind = d_kind.p;
     launch_fol_kind(a, r->v.stream);
     if ((e = hipGetLastError()) == hipSuccess)
-        e = hipMemcpyAsync(kinds, d_kind, (size_t)L, hipMemcpyDeviceToHost, r->v.stream);
+        e = hipMemcpyAsync(kinds, d_kind.p, (size_t)L, hipMemcpyDeviceToHost, r->v.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(r->v.stream);
-    (void)hipFree(d_kind);
     if (e != hipSuccess) return fol_hip_fail(c, "fol_kind_kernel", e);
     return PDEVAL_OK;
 }
@@ -804,16 +663,7 @@ extern "C" int pdeval_fol_registry_load(pdeval_ctx* c, pdeval_fol_registry* r, c
     hipError_t e = hipSetDevice(r->v.device);
     if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
     if ((rc = reg_reserve(r, n_classes)) != PDEVAL_OK) return rc;
-    FolMoveArgs m{};
-    reg_move_args(r, &m);
-    m.base = 0;
-    m.n_lead = n_classes;
-    m.fields = const_cast<double*>(d_fields);
-    m.n_rows = n_classes;
-    m.to_store = 1;
-    launch_fol_move(m, r->v.stream);
-    if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
-    if ((e = hipStreamSynchronize(r->v.stream)) != hipSuccess) return fol_hip_fail(c, "fol_move_kernel", e);
+    if ((rc = reg_move(r, 0, n_classes, const_cast<double*>(d_fields), n_classes, nullptr, true)) != PDEVAL_OK) return rc;
     r->book.load(leader_keys, sizes, n_classes);
     return PDEVAL_OK;
 }

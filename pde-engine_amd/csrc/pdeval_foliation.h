@@ -6,13 +6,15 @@
 // runs on gradient fields sampled on a small m x m grid: fol_field_kernel computes them from the
 // resident programs, fol_match_kernel applies the scaled zero test of J to rows of fields against
 // up to 32 probe fields, and fol_round groups rows into classes from the resulting masks.  A
-// registry (pdeval_fol_registry.hip) keeps the leaders' fields on the device across batches:
-// fol_assign_kernel finds each row's first match among them (fol_chunk_test, fol_store_at).
+// registry (pdeval_fol_registry.hip) keeps the leaders' fields on the device across batches: one
+// pair scan (fol_chunk_test, fol_store_at) finds each row's first match among them
+// (fol_assign_kernel) or every match (fol_link_kernel).
 //
-// This header holds the per-point code of both kernels and the leader round, which also compile
+// This header holds the per-point code of the kernels and the leader round, which also compile
 // for the host under -DPD_HOST_SIM (tests/hostsim/sim_foliation.cpp, sim_foliation_field.cpp),
-// the kernels' argument blocks and the launchers of pdeval_foliation.hip.
+// the kernels' argument blocks, the launchers and the owning device buffer of the entry points.
 #pragma once
+#include <utility>
 #include <vector>
 
 #include "pdeval_kernels.h"
@@ -260,39 +262,34 @@ struct FolFieldArgs {
 };
 void launch_fol_field(const FolFieldArgs& a, hipStream_t s);
 
-// Stage A of a registry (pdeval_fol_registry.hip): first[row] = the smallest leader index the row
-// matches, -1 if none (or n_finite[row] < min_points, when given)
-struct FolAssignArgs {
+// The pair scan of a registry (pdeval_fol_registry.hip, fol_scan): rows of fields against the
+// resident leaders.  What both of its modes take.
+struct FolScanArgs {
     const double* rows;        // row fields, [n_rows][2][mm]
     int64_t n_rows;
-    const int32_t* n_finite;   // optional, n_rows
     const double* store;       // the leader store, chunk-major (fol_store_at)
     int64_t cap, L;            // its capacity and the leaders it holds
     int mm, n_chunk;
     double tau;
     int min_points;
+    uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernels' AXIS instantiations
+};
+// Stage A: first[row] = the smallest leader index the row matches, -1 if none (or
+// n_finite[row] < min_points, when given)
+struct FolAssignArgs : FolScanArgs {
+    const int32_t* n_finite;   // optional, n_rows
     int64_t* first;            // n_rows
-    uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernel's AXIS instantiations
 };
 void launch_fol_assign(const FolAssignArgs& a, hipStream_t s);
-
-// The link pass of a registry (pdeval_fol_registry.hip, DESIGN.md §14 "Links and components"):
-// for every leader l < lim[row], l != cls[row], that the row matches, the pair (cls[row], l) is
-// appended to edges.  A row with cls[row] < 0 yields none.
-struct FolLinkArgs {
-    const double* rows;        // row fields, [n_rows][2][mm]
-    int64_t n_rows;
+// The link pass (DESIGN.md §14 "Links and components"): for every leader l < lim[row],
+// l != cls[row], that the row matches, the pair (cls[row], l) is appended to edges.  A row with
+// cls[row] < 0 yields none.
+struct FolLinkArgs : FolScanArgs {
     const int32_t* cls;        // n_rows, each -1 or in [0, L) (checked by the host before the launch)
     const int32_t* lim;        // n_rows, each in [0, L] (likewise)
-    const double* store;       // the leader store, chunk-major (fol_store_at)
-    int64_t cap, L;            // its capacity and the leaders it holds
-    int mm, n_chunk;
-    double tau;
-    int min_points;
     int32_t* edges;            // [ecap][2]
     int64_t ecap;
     unsigned long long* count; // edges found, zeroed by the caller; those past ecap are counted, not stored
-    uint32_t flags;            // PDEVAL_FOL_AXIS selects the kernel's AXIS instantiations
 };
 void launch_fol_link(const FolLinkArgs& a, hipStream_t s);
 
@@ -323,6 +320,38 @@ struct FolKindArgs {
     uint8_t* kind;             // n_rows
 };
 void launch_fol_kind(const FolKindArgs& a, hipStream_t s);
+
+// ---------------------------------------------------------------- host side
+// An owning device buffer of `cap` elements.  It grows by a new allocation and copies nothing
+// (the leader store's growth copies for itself and swaps the new block in); the destructor
+// frees, on the device that is current then.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    int64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    // room for n elements; false (the old block and capacity untouched, no HIP error left
+    // pending) when the allocation fails
+    bool reserve(int64_t n) {
+        if (n <= cap) return true;
+        T* q = nullptr;
+        if (hipMalloc((void**)&q, (size_t)n * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        (void)hipFree(p);
+        p = q;
+        cap = n;
+        return true;
+    }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+};
 
 // what the entry points (pdeval_foliation.hip, pdeval_fol_registry.hip) need of a context (pdeval.hip)
 struct FolCtx {

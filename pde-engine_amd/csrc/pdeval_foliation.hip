@@ -154,19 +154,10 @@ extern "C" int pdeval_default_fol_params(pdeval_fol_params* p) {
 extern "C" int pdeval_jacobian_match(pdeval_ctx* c, const double* d_rows_field, int64_t n_rows,
                                      const double* d_probe_field, int n_probe, const pdeval_fol_params* params,
                                      uint32_t* d_mask, int32_t* d_n_used, double* d_qmax, void* stream) {
-    if (!c) return fol_fail(nullptr, PDEVAL_ERR_ARG, "pdeval_jacobian_match: null context");
     FolCtx v;
-    fol_ctx(c, &v);
-    if (v.problem != PDEVAL_PROBLEM_FORCE_FREE)
-        return fol_fail(c, PDEVAL_ERR_ARG,
-                        "pdeval_jacobian_match: foliation classes are a force-free notion (the Kerr equation is "
-                        "linear: u -> f(u) is no symmetry of it)");
     pdeval_fol_params prm;
-    if (params) prm = *params;
-    else pdeval_default_fol_params(&prm);
-    if (prm.m < 4 || prm.m > 64 || prm.min_points < 1 || !(prm.tau >= 0.0) || !std::isfinite(prm.tau))
-        return fol_fail(c, PDEVAL_ERR_ARG,
-                        "pdeval_jacobian_match: bad parameters (4 <= m <= 64, min_points >= 1, tau >= 0 finite)");
+    const int rc = fol_check(c, "pdeval_jacobian_match", nullptr, 0, nullptr, 0, 0, params, &v, &prm);
+    if (rc != PDEVAL_OK) return rc;
     if (n_probe > PDEVAL_FOL_MAX_PROBES)
         return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_jacobian_match: more than PDEVAL_FOL_MAX_PROBES probes");
     if (n_rows < 0 || n_probe < 0 || n_rows > PDEVAL_MAX_BATCH ||
@@ -174,7 +165,7 @@ extern "C" int pdeval_jacobian_match(pdeval_ctx* c, const double* d_rows_field, 
         return fol_fail(c, PDEVAL_ERR_ARG, "pdeval_jacobian_match: bad argument");
     if (n_rows == 0) return PDEVAL_OK;
     hipError_t e = hipSetDevice(v.device);
-    if (e != hipSuccess) return fol_fail(c, PDEVAL_ERR_HIP, (std::string("hipSetDevice: ") + hipGetErrorString(e)).c_str());
+    if (e != hipSuccess) return fol_hip_fail(c, "hipSetDevice", e);
     FolMatchArgs a{};
     a.rows = d_rows_field;
     a.n_rows = n_rows;
@@ -189,7 +180,7 @@ extern "C" int pdeval_jacobian_match(pdeval_ctx* c, const double* d_rows_field, 
     a.flags = (uint32_t)prm.flags;
     launch_fol_match(a, stream ? (hipStream_t)stream : v.stream);
     e = hipGetLastError();
-    if (e != hipSuccess) return fol_fail(c, PDEVAL_ERR_HIP, (std::string("fol_match_kernel: ") + hipGetErrorString(e)).c_str());
+    if (e != hipSuccess) return fol_hip_fail(c, "fol_match_kernel", e);
     return PDEVAL_OK;
 }
 
@@ -340,51 +331,31 @@ extern "C" int pdeval_foliation_classes(pdeval_ctx* c, const int32_t* d_ops, int
     const hipStream_t s = v.stream;
     const int mm = prm.m * prm.m;
     // device buffers: the fields of the whole list (never copied to the host), the finite
-    // counts, the round's row indices and its masks
-    double* d_field = nullptr;
-    int32_t* d_nfin = nullptr;
-    int64_t* d_idx = nullptr;
-    uint32_t* d_mask = nullptr;
-    auto release = [&]() {
-        (void)hipFree(d_field);
-        (void)hipFree(d_nfin);
-        (void)hipFree(d_idx);
-        (void)hipFree(d_mask);
-    };
-    const size_t field_bytes = (size_t)n_list * 2 * (size_t)mm * sizeof(double);
-    if (hipMalloc((void**)&d_field, field_bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    // counts, the round's row indices and its masks; freed when the call returns
+    DevBuf<double> d_field;
+    DevBuf<int32_t> d_nfin;
+    DevBuf<int64_t> d_idx;
+    DevBuf<uint32_t> d_mask;
+    const int64_t field_doubles = n_list * 2 * (int64_t)mm;
+    if (!d_field.reserve(field_doubles))
         return fol_fail(c, PDEVAL_ERR_ALLOC,
-                        ("pdeval_foliation_classes: cannot allocate " + std::to_string(field_bytes) +
+                        ("pdeval_foliation_classes: cannot allocate " + std::to_string((size_t)field_doubles * sizeof(double)) +
                          " bytes of gradient fields (n_list x 2 m^2 x 8): classify a shorter list or a smaller m")
                             .c_str());
-    }
-    if (hipMalloc((void**)&d_nfin, (size_t)n_list * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&d_idx, (size_t)n_list * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void**)&d_mask, (size_t)n_list * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        release();
+    if (!d_nfin.reserve(n_list) || !d_idx.reserve(n_list) || !d_mask.reserve(n_list))
         return fol_fail(c, PDEVAL_ERR_ALLOC, "pdeval_foliation_classes: cannot allocate the round buffers");
-    }
-    auto hip_fail = [&](const char* what, hipError_t err) {
-        release();
-        return fol_hip_fail(c, what, err);
-    };
-    rc = fol_fields_launch(c, v, prm, d_ops, n_words, d_offsets, n, d_list, n_list, d_field, d_nfin, s);
-    if (rc != PDEVAL_OK) {
-        release();
-        return rc;
-    }
+    rc = fol_fields_launch(c, v, prm, d_ops, n_words, d_offsets, n, d_list, n_list, d_field.p, d_nfin.p, s);
+    if (rc != PDEVAL_OK) return rc;
     std::vector<int32_t> nfin((size_t)n_list);
     std::vector<int64_t> list;
     if (d_list) {
         list.resize((size_t)n_list);
         if ((e = hipMemcpyAsync(list.data(), d_list, (size_t)n_list * sizeof(int64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
-            return hip_fail("hipMemcpyAsync", e);
+            return fol_hip_fail(c, "hipMemcpyAsync", e);
     }
-    if ((e = hipMemcpyAsync(nfin.data(), d_nfin, (size_t)n_list * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
-        return hip_fail("hipMemcpyAsync", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("fol_field_kernel", e);
+    if ((e = hipMemcpyAsync(nfin.data(), d_nfin.p, (size_t)n_list * sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+        return fol_hip_fail(c, "hipMemcpyAsync", e);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return fol_hip_fail(c, "fol_field_kernel", e);
     // rows with too few finite points are unclassified; the others wait for a round
     std::vector<int64_t> un;
     for (int64_t r = 0; r < n_list; ++r) {
@@ -393,12 +364,8 @@ extern "C" int pdeval_foliation_classes(pdeval_ctx* c, const int32_t* d_ops, int
     }
     int64_t classes = 0;
     int32_t rounds = 0;
-    rc = fol_rounds(c, d_field, mm, prm, un, d_list ? list.data() : nullptr, leader, d_idx, d_mask, s, &classes, &rounds);
-    if (rc != PDEVAL_OK) {
-        release();
-        return rc;
-    }
-    release();
+    rc = fol_rounds(c, d_field.p, mm, prm, un, d_list ? list.data() : nullptr, leader, d_idx.p, d_mask.p, s, &classes, &rounds);
+    if (rc != PDEVAL_OK) return rc;
     if (n_classes) *n_classes = classes;
     if (n_rounds) *n_rounds = rounds;
     return PDEVAL_OK;

@@ -159,6 +159,59 @@ def test_seventy_leaders(ctx, seventy, m, n_rows):
         assert reg.link_fields(_dev(rows), want) == 0      # the leaders all existed: nothing to complete
 
 
+# ---------------------------------------------------------------- the link scan at the tile edges
+def _tile_edge_rows(ctx, m, n_lead):
+    """(n_lead resident leaders, a batch of six rows, its ids): the leaders are the left halves of
+    the foliations u = rho**2 + k z**2, k = 1 .. n_lead.  The batch: the right halves of two
+    further foliations (new leaders n_lead and n_lead + 1), a full-domain row that is foliation 3 on
+    the left half and the second new leader's on the right (class 3, link {3, n_lead + 1}), an
+    all-NaN row, a multiple of the last resident leader and the first new foliation everywhere.
+    By the arrival rule rows 0 .. 2, in one block with the all-NaN row, scan n_lead, n_lead + 1
+    and n_lead + 2 leaders."""
+    rho, z = _grid(ctx, m)
+    left, right = _halves(m * m)
+    fol = [np.stack([2.0 * rho, 2.0 * (1.0 + k) * z]) for k in range(n_lead + 2)]
+    lead = np.stack([K.masked(f, left) for f in fol[:n_lead]])
+    rows = np.stack([K.masked(fol[n_lead], right), K.masked(fol[n_lead + 1], right),
+                     np.where(left, fol[3], fol[n_lead + 1]), np.full((2, m * m), np.nan),
+                     -0.5 * lead[n_lead - 1], 2.5 * fol[n_lead]])
+    return lead, rows, [n_lead, n_lead + 1, 3, -1, n_lead - 1, n_lead]
+
+
+@pytest.mark.parametrize('n_lead', (T - 2, T, 2 * T - 1))
+@pytest.mark.parametrize('m', (16, 20))
+def test_link_scan_at_tile_edges(ctx, m, n_lead):
+    """The link mode of the scan with T - 2, T and 2 T - 1 resident leaders, m = 16 (REG) and
+    m = 20: the scan limits of the rows of one block differ and lie on both sides of a tile's
+    end, and the link joins a leader of the first tile to one past it (n_lead >= T).  Then
+    link_fields over the same rows with the bridging row's id set to -1 -- on the same registry,
+    where nothing is new, and on one without FOL_LINK, where the bridging row is the only source
+    of the link.  Ids, links and components are the restatement's; the restatement alone is
+    checked first."""
+    lead, rows, ids = _tile_edge_rows(ctx, m, n_lead)
+    without = np.array(ids)
+    without[2] = -1
+    for flags in (FOL_LINK, 0):
+        prm = _params(m, flags)
+        ref = _ref(prm)
+        assert ref.assign(lead).tolist() == list(range(n_lead)) and not ref.links
+        want = ref.assign(rows)
+        assert want.tolist() == ids and ref.links == ({(3, n_lead + 1)} if flags else set())
+        assert n_lead < T or (n_lead + 1) // T > 3 // T          # the link crosses a tile's end
+        with ctx.fol_registry(prm) as reg:
+            assert reg.assign_fields(_dev(lead)).tolist() == list(range(n_lead)) and reg.n_links == 0
+            assert np.array_equal(reg.assign_fields(_dev(rows)), want)
+            _same(reg, ref)
+            n_new = ref.link_fields(rows, without)               # the -1 rows yield nothing
+            assert n_new == 0 and len(ref.links) == (1 if flags else 0)
+            assert reg.link_fields(_dev(rows), without) == n_new
+            _same(reg, ref)
+            n_new = ref.link_fields(rows, want)
+            assert n_new == (0 if flags else 1) and ref.links == {(3, n_lead + 1)}
+            assert reg.link_fields(_dev(rows), want) == n_new
+            _same(reg, ref)
+
+
 # ---------------------------------------------------------------- the arrival rule
 def test_arrival_rule_and_link_fields(ctx):
     """A row placed before the second leader yields no link in assign; link_fields, which tests
