@@ -10,6 +10,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -24,6 +25,7 @@
 #include "pdeval_tier2.h"
 #include "pdeval_launch.h"
 #include "pdeval_foliation.h"
+#include "pdeval_scratch.h"
 
 using namespace pd;
 
@@ -74,33 +76,93 @@ namespace {
 struct Grid {
     double x_lo, x_hi, nx, y_lo, y_hi, ny, x_ph, y_ph;
 };
+
+// Owners of a context's HIP objects.  Each releases what it holds in its destructor, on the
+// device that is current then (pdeval_destroy sets it).
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+struct Stream : NoCopy {
+    hipStream_t s = nullptr;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+template <int N>
+struct Events : NoCopy {   // all of them or none
+    hipEvent_t e[N] = {};
+    ~Events() { clear(); }
+    void clear() {
+        for (hipEvent_t& x : e) {
+            if (x) (void)hipEventDestroy(x);
+            x = nullptr;
+        }
+    }
+    hipError_t create(unsigned flags) {
+        for (hipEvent_t& x : e) {
+            const hipError_t err = hipEventCreateWithFlags(&x, flags);
+            if (err != hipSuccess) {
+                x = nullptr;
+                clear();
+                return err;
+            }
+        }
+        return hipSuccess;
+    }
+};
+struct Pinned : NoCopy {   // a pinned host block, allocated once
+    uint8_t* p = nullptr;
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t bytes) { return hipHostMalloc((void**)&p, bytes, hipHostMallocDefault); }
+};
+// the captured launch chains of small host batches (validate_small), by key; an entry is stale
+// once the context's buf_epoch has moved past its own
+struct Graphs : NoCopy {
+    struct Entry {
+        hipGraphExec_t exec = nullptr;
+        uint64_t epoch = 0;
+    };
+    std::map<uint64_t, Entry> m;
+    ~Graphs() { clear(); }
+    void clear() {
+        for (auto& g : m) (void)hipGraphExecDestroy(g.second.exec);
+        m.clear();
+    }
+};
 }  // namespace
 
+// Members are destroyed in reverse order of declaration, and pdeval_destroy relies on it: the
+// streams come first and the events next (destroyed last, after pdeval_destroy has synchronized
+// both streams), every device and pinned buffer after them, and the graph executables, which
+// reference those buffers and are launched on `stream`, last (destroyed first).
 struct pdeval_ctx {
     int device = 0;
     int problem = 0;
     int n_ref = 0, n_pts = 0;
     int fp_pts[PDEVAL_FP_N] = {0, 0, 0, 0};
-    hipStream_t stream = nullptr;
+    Stream stream;
     // the early double-double tier runs on `side`, forked after the point stage and joined
     // before the classes are final (env PDEVAL_DD_EARLY=0: one tier after the grid, A/B)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Stream side;
+    Events<2> ev_fj;                  // e[0] the fork, e[1] the join
+    // optional per-pass timing (pdeval_set_timing): an event before every pass and one after
+    // the last, recorded on the launch stream
+    Events<PDEVAL_N_PASSES + 1> ev;
+    bool timing = false;
+    int ev_recorded = 0;
     bool dd_early = true;
     int list_queue = PD_LIST_QUEUE;   // list passes: 0 static schedule, k > 0 queue chunks of k items
     int list_parts = PD_LIST_PARTS;   // list passes: waves per candidate at full size
-    uint8_t* d_ddps = nullptr;      // the early tier's classes, capacity cap
-    double* d_dd_res = nullptr;     // speculative provisional passes' outputs (cap * 4, cap)
-    double* d_dd_q = nullptr;
     bool dd_spec = true;            // env PDEVAL_DD_SPEC=0: provisional passes after the grid (A/B)
     double ref_x[4] = {0, 0, 0, 0}, ref_y[4] = {0, 0, 0, 0};
     dd ref_xd[4] = {}, ref_yd[4] = {};   // the reference points as double-doubles
     dd kc_ref[16] = {};                  // Kerr operator coefficients there, double-double
     int nx = 0, ny = 0;
-    double* d_gx = nullptr;   // nx grid abscissae
-    double* d_gy = nullptr;   // ny grid ordinates
-    double* d_kc = nullptr;
-    double* d_ptab = nullptr;            // coordinate-power tables of the lean passes
+    DevBuf<double> d_gx;      // nx grid abscissae, then their reciprocals
+    DevBuf<double> d_gy;      // ny grid ordinates
+    DevBuf<double> d_kc;
+    DevBuf<double> d_ptab;               // coordinate-power tables of the lean passes
     Grid grid{};                         // as given, or the problem's default (grid_default)
     bool grid_default = true;
     // the problem's constants (Kerr M, a; pdeval_kerr_constants) and their per-stage tables
@@ -109,67 +171,32 @@ struct pdeval_ctx {
     PrmTab<dd> prm_pt_dd{}, prm_grid_dd{};
     double ct_x[8] = {}, ct_y[8] = {};   // Kerr constant-test points
     int n_ct = 0;
-    // scratch: work lists and their counters
-    int64_t cap = 0;
-    // device work lists (capacity cap each) and their counters d_counts[L_*]
-    int64_t* d_list[PD_N_LISTS] = {};
-    int32_t* d_counts = nullptr;
-    uint8_t* d_pstate = nullptr;    // point-stage state, capacity cap
-    int32_t* d_dec = nullptr;       // decoded programs of the lean grid passes, dec_cap words
-    int64_t dec_cap = 0;
-    // the hoisted prefixes / segments of the lean passes (pdeval_grid.h PD_HOIST): 8 x
-    // kHoistPool slots of hoist_stride doubles and their owner words, whatever the batch size
-    // (env PDEVAL_HOIST=0: none, A/B)
-    bool hoist = true;
+    // the batch-sized scratch and its sizes (pdeval_scratch.h; cfg holds the A/B switches
+    // PDEVAL_HOIST, PDEVAL_HOIST_SLOTS and PDEVAL_TIER2_MASK)
+    ScratchCfg cfg;
+    Scratch scr;
+    DevBuf<int32_t> d_counts;           // the lists' counters d_counts[L_*], then errw and the queue heads
     bool hoist_sub = true;              // env PDEVAL_HOIST_SUB=0: no hoisted segments (A/B)
-    double* d_hoist = nullptr;
-    uint32_t* d_hoist_own = nullptr;
-    bool hoist_slots = true;            // env PDEVAL_HOIST_SLOTS=0: one slot per candidate (A/B)
-    int32_t* d_hseg = nullptr;          // the decoder's hoisted segments, cap x 4 words
-    // the lean passes' failing lanes per candidate and grid chunk, cap x chunks words, which
-    // tier 2 re-checks instead of the whole grid (env PDEVAL_TIER2_MASK=0: none, A/B)
-    bool tier2_mask = true;
-    uint64_t* d_fsum = nullptr;         // ... and per candidate the chunks whose word was stored
     int deep_parts = PD_DEEP_PARTS;     // the stack-8 lists' waves per candidate (env PDEVAL_DEEP_PARTS)
-    uint64_t* d_fmask = nullptr;
-    uint8_t* d_status = nullptr;    // classes when the caller asks for no status output
-    double* d_noise = nullptr;      // fp64 noise bounds at the reference points, cap * 4
-    T2Acc* d_t2acc = nullptr;       // tier-2 accumulators, cap entries, zero between launches
-    // shape sort of the batch (pdeval_sort.hip): keys 2 x cap, permutation 2 x cap, scratch
-    bool sort = true;               // env PDEVAL_SORT=0 turns it off (measurements)
+    bool sort = true;               // env PDEVAL_SORT=0 turns the shape sort off (measurements)
     bool lean_cplx = true;          // env PDEVAL_LEAN_CPLX=0: the generic complex pass (A/B)
-    uint64_t* d_skeys = nullptr;
-    int32_t* d_sidx = nullptr;
-    void* d_stemp = nullptr;
-    size_t stemp_bytes = 0;
-    // host-path staging
-    int64_t hcap_words = 0, hcap_n = 0;
-    int32_t* d_ops = nullptr;
-    int64_t* d_off = nullptr;
-    uint8_t* d_outbuf = nullptr;
-    int64_t outbuf_bytes = 0;
+    // host-path staging: a batch's programs, offsets and output block (outbuf_layout)
+    DevBuf<int32_t> d_ops;
+    DevBuf<int64_t> d_off;
+    DevBuf<uint8_t> d_outbuf;
+    Pinned h_errw;                 // the device error word after a direct-path call
+    Pinned h_stage;                // validate_small: ops + offsets in, the output block out
     std::string err;
-    // small host batches (validate_small): the launch chain captured once per (n, params) as
-    // a HIP graph, inputs and outputs through pinned staging; graphs are dropped whenever a
-    // buffer they reference is reallocated (buf_epoch)
-    bool use_graph = true;          // env PDEVAL_GRAPH=0 turns it off
-    uint64_t buf_epoch = 0;
-    void* h_errw = nullptr;        // pinned word: the device error word after a direct-path call
-    struct GraphEntry {
-        hipGraphExec_t exec = nullptr;
-        uint64_t epoch = 0;
-    };
-    std::map<uint64_t, GraphEntry> graphs;
-    uint8_t* h_stage = nullptr;     // pinned: ops + offsets in, the output block out
-    size_t h_stage_bytes = 0;
-    // optional per-pass timing (pdeval_set_timing): an event before every pass and one after
-    // the last, recorded on the launch stream
-    bool timing = false;
-    hipEvent_t ev[PDEVAL_N_PASSES + 1] = {};
-    int ev_recorded = 0;
     // the multi-GPU exchange (pdeval_comm_init)
     ncclComm_t comm = nullptr;
     int world = 1, rank = 0;
+    // small host batches (validate_small): the launch chain captured once per (n, params) as
+    // a HIP graph, inputs and outputs through pinned staging.  buf_epoch advances whenever a
+    // buffer moves (DevBuf::replace, for every buffer above) or the constants that graphs hold
+    // by value change (build_points); a graph of an older epoch is dropped, not replayed.
+    bool use_graph = true;          // env PDEVAL_GRAPH=0 turns it off
+    uint64_t buf_epoch = 0;
+    Graphs graphs;
 };
 
 // RCCL, loaded on first use (dlopen: a process that already holds librccl.so.1, e.g. through
@@ -352,7 +379,7 @@ static int build_points(pdeval_ctx* c) {
         HIPCHK(c, hipMemcpy(c->d_kc, kc.data(), kc.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     // the lean passes' coordinate-power tables, from the grid just uploaded (same JetOps::pcoefs)
-    if (!c->d_ptab) HIPCHK(c, hipMalloc(&c->d_ptab, ptab_bytes(c->problem, nx, ny)));
+    HIPCHK(c, c->d_ptab.replace((int64_t)(ptab_bytes(c->problem, nx, ny) + 7) / 8, c->buf_epoch));
     launch_ptab(c->problem, c->d_gx, c->d_gy, nx, ny, c->d_ptab, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -451,22 +478,26 @@ extern "C" int pdeval_create(int device_id, int problem_id, const double* grid, 
     if (const char* v = getenv("PDEVAL_DD_SPEC")) c->dd_spec = atoi(v) != 0;
     if (const char* v = getenv("PDEVAL_LIST_QUEUE")) c->list_queue = std::max(0, atoi(v));
     if (const char* v = getenv("PDEVAL_LIST_PARTS")) c->list_parts = std::min(16, std::max(1, atoi(v)));
-    if (const char* v = getenv("PDEVAL_HOIST")) c->hoist = atoi(v) != 0;
+    if (const char* v = getenv("PDEVAL_HOIST")) c->cfg.hoist = atoi(v) != 0;
     if (const char* v = getenv("PDEVAL_HOIST_SUB")) c->hoist_sub = atoi(v) != 0;
-    if (const char* v = getenv("PDEVAL_HOIST_SLOTS")) c->hoist_slots = atoi(v) != 0;
-    if (const char* v = getenv("PDEVAL_TIER2_MASK")) c->tier2_mask = atoi(v) != 0;
+    if (const char* v = getenv("PDEVAL_HOIST_SLOTS")) c->cfg.hoist_slots = atoi(v) != 0;
+    if (const char* v = getenv("PDEVAL_TIER2_MASK")) c->cfg.tier2_mask = atoi(v) != 0;
+    // per hoist slot: the prefix's pure coefficients (K + 1 rows of 64) and the segment's whole
+    // jet (nc(K) rows of 64, Kerr only) -- pd::hoist_stride
+    c->cfg.hoist_pool_slots = 8 * pd::kHoistPool;
+    c->cfg.hoist_stride = pd::hoist_stride(problem_id == PDEVAL_PROBLEM_FORCE_FREE ? 4 : 2);
+    c->cfg.fmask_words = (int64_t)nx * (ny / 64);
+    c->cfg.t2acc_bytes = sizeof(T2Acc);
+    c->cfg.sort_temp_bytes = sort_temp_bytes;
     if (const char* v = getenv("PDEVAL_DEEP_PARTS")) c->deep_parts = atoi(v) > 1 ? PD_DEEP_PARTS : 1;
-    if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking)) != hipSuccess)
         return fail("hipStreamCreate", e);
-    if ((e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = hipStreamCreateWithFlags(&c->side.s, hipStreamNonBlocking)) != hipSuccess)
         return fail("hipStreamCreate", e);
-    if ((e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess)
-        return fail("hipEventCreate", e);
-    if ((e = hipMalloc(&c->d_gx, 2 * nx * sizeof(double))) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMalloc(&c->d_gy, ny * sizeof(double))) != hipSuccess) return fail("hipMalloc", e);
-    if (problem_id == PDEVAL_PROBLEM_KERR &&
-        (e = hipMalloc(&c->d_kc, 8 * (size_t)c->n_pts * sizeof(double))) != hipSuccess)
+    if ((e = c->ev_fj.create(hipEventDisableTiming)) != hipSuccess) return fail("hipEventCreate", e);
+    if ((e = c->d_gx.replace(2 * nx, c->buf_epoch)) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = c->d_gy.replace(ny, c->buf_epoch)) != hipSuccess) return fail("hipMalloc", e);
+    if (problem_id == PDEVAL_PROBLEM_KERR && (e = c->d_kc.replace(8 * (int64_t)c->n_pts, c->buf_epoch)) != hipSuccess)
         return fail("hipMalloc", e);
     if (problem_id == PDEVAL_PROBLEM_KERR) pdeval_default_kerr_constants(&c->kconst);
     if (int rc = build_points(c)) {
@@ -475,7 +506,7 @@ extern "C" int pdeval_create(int device_id, int problem_id, const double* grid, 
         return rc;
     }
     // the list counters and, after them, the device error word (KernelArgs::errw)
-    if ((e = hipMalloc(&c->d_counts, PD_COUNT_WORDS * sizeof(int32_t))) != hipSuccess) return fail("hipMalloc", e);
+    if ((e = c->d_counts.replace(PD_COUNT_WORDS, c->buf_epoch)) != hipSuccess) return fail("hipMalloc", e);
     *out = c;
     return PDEVAL_OK;
 }
@@ -483,40 +514,10 @@ extern "C" int pdeval_create(int device_id, int problem_id, const double* grid, 
 extern "C" int pdeval_destroy(pdeval_ctx* c) {
     if (!c) return PDEVAL_ERR_ARG;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->side) (void)hipStreamSynchronize(c->side);
+    if (c->stream.s) (void)hipStreamSynchronize(c->stream);
+    if (c->side.s) (void)hipStreamSynchronize(c->side);
     if (c->comm) pdeval_comm_destroy(c);
-    for (int64_t* l : c->d_list)
-        if (l) (void)hipFree(l);
-    if (c->d_pstate) (void)hipFree(c->d_pstate);
-    if (c->d_ddps) (void)hipFree(c->d_ddps);
-    if (c->d_dd_res) (void)hipFree(c->d_dd_res);
-    if (c->d_dd_q) (void)hipFree(c->d_dd_q);
-    if (c->d_dec) (void)hipFree(c->d_dec);
-    if (c->d_hoist) (void)hipFree(c->d_hoist);
-    if (c->d_hoist_own) (void)hipFree(c->d_hoist_own);
-    if (c->d_hseg) (void)hipFree(c->d_hseg);
-    if (c->d_fmask) (void)hipFree(c->d_fmask);
-    if (c->d_fsum) (void)hipFree(c->d_fsum);
-    if (c->d_status) (void)hipFree(c->d_status);
-    if (c->d_noise) (void)hipFree(c->d_noise);
-    if (c->d_t2acc) (void)hipFree(c->d_t2acc);
-    if (c->d_skeys) (void)hipFree(c->d_skeys);
-    if (c->d_sidx) (void)hipFree(c->d_sidx);
-    if (c->d_stemp) (void)hipFree(c->d_stemp);
-    for (void* p : {(void*)c->d_gx, (void*)c->d_gy, (void*)c->d_kc, (void*)c->d_ptab,
-                    (void*)c->d_counts, (void*)c->d_ops, (void*)c->d_off, (void*)c->d_outbuf})
-        if (p) (void)hipFree(p);
-    for (auto& g : c->graphs)
-        if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_errw) (void)hipHostFree(c->h_errw);
-    for (hipEvent_t& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    // everything else belongs to a member, released in the order pdeval_ctx states
     delete c;
     return PDEVAL_OK;
 }
@@ -771,7 +772,15 @@ extern "C" double pdeval_program_hoist_flops(int problem_id, const int32_t* ops,
 }
 
 // ---------------------------------------------------------------------------- launches
-static void copy_constants(const pdeval_ctx* c, KernelArgs& a) {
+// the part of KernelArgs that depends on the context alone
+static void ctx_args(const pdeval_ctx* c, KernelArgs& a) {
+    for (int k = 0; k < 4; ++k) {
+        a.ref_x[k] = c->ref_x[k];
+        a.ref_y[k] = c->ref_y[k];
+        a.ref_xd[k] = c->ref_xd[k];
+        a.ref_yd[k] = c->ref_yd[k];
+    }
+    for (int k = 0; k < 16; ++k) a.kc_ref[k] = c->kc_ref[k];
     a.prm_pt = c->prm_pt;
     a.prm_grid = c->prm_grid;
     a.prm_pt_dd = c->prm_pt_dd;
@@ -781,93 +790,10 @@ static void copy_constants(const pdeval_ctx* c, KernelArgs& a) {
         a.ct_x[k] = c->ct_x[k];
         a.ct_y[k] = c->ct_y[k];
     }
-}
-
-// the decoded-program array of the lean grid passes: as many words as the batch's programs
-// (grown when a batch outgrows it, like the work lists; never inside a sized call)
-static int ensure_dec(pdeval_ctx* c, int64_t n_words) {
-    if (n_words <= c->dec_cap) return PDEVAL_OK;
-    ++c->buf_epoch;
-    if (c->d_dec) (void)hipFree(c->d_dec);
-    c->d_dec = nullptr;
-    c->dec_cap = 0;
-    const int64_t cap = n_words < 4096 ? 4096 : n_words;
-    // + 4 words: the lean interpreter reads an opcode word with the two after it (pdeval_grid.h)
-    HIPCHK(c, hipMalloc(&c->d_dec, (cap + 4) * sizeof(int32_t)));
-    c->dec_cap = cap;
-    return PDEVAL_OK;
-}
-
-static int ensure_scratch(pdeval_ctx* c, int64_t n) {
-    if (n <= c->cap) return PDEVAL_OK;
-    ++c->buf_epoch;
-    for (int64_t*& l : c->d_list) {
-        if (l) (void)hipFree(l);
-        l = nullptr;
-    }
-    c->cap = 0;
-    const int64_t cap = n < 1024 ? 1024 : n;
-    for (int64_t*& l : c->d_list) HIPCHK(c, hipMalloc(&l, cap * sizeof(int64_t)));
-    if (c->d_pstate) (void)hipFree(c->d_pstate);
-    c->d_pstate = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_pstate, cap));
-    if (c->d_ddps) (void)hipFree(c->d_ddps);
-    c->d_ddps = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_ddps, cap));
-    if (c->d_dd_res) (void)hipFree(c->d_dd_res);
-    if (c->d_dd_q) (void)hipFree(c->d_dd_q);
-    c->d_dd_res = c->d_dd_q = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_dd_res, cap * 4 * sizeof(double)));   // (n_ref <= 4)
-    HIPCHK(c, hipMalloc(&c->d_dd_q, cap * sizeof(double)));
-    if (c->d_hseg) (void)hipFree(c->d_hseg);
-    c->d_hseg = nullptr;
-    if (c->hoist) {
-        // per slot (8 pools of kHoistPool, one per XCD; pdeval_grid.h hoist_acquire): the
-        // prefix's pure coefficients (K + 1 rows of 64) and the segment's whole jet (nc(K) rows
-        // of 64, Kerr only) -- pd::hoist_stride; allocated once, it does not grow with the batch
-        const int K = c->problem == PDEVAL_PROBLEM_FORCE_FREE ? 4 : 2;
-        if (c->hoist_slots && !c->d_hoist) {
-            HIPCHK(c, hipMalloc(&c->d_hoist, (size_t)8 * pd::kHoistPool * pd::hoist_stride(K) * sizeof(double)));
-            HIPCHK(c, hipMalloc(&c->d_hoist_own, (size_t)8 * pd::kHoistPool * sizeof(uint32_t)));
-            HIPCHK(c, hipMemset(c->d_hoist_own, 0, (size_t)8 * pd::kHoistPool * sizeof(uint32_t)));   // all free
-        } else if (!c->hoist_slots) {   // (A/B: the round-5 layout, one slot per candidate)
-            if (c->d_hoist) (void)hipFree(c->d_hoist);
-            c->d_hoist = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_hoist, (size_t)std::max<int64_t>(cap, 8 * pd::kHoistPool) * pd::hoist_stride(K) * sizeof(double)));
-        }
-        // the decoder's per-candidate segment records
-        HIPCHK(c, hipMalloc(&c->d_hseg, (size_t)cap * 4 * sizeof(int32_t)));
-    }
-    if (c->d_fmask) (void)hipFree(c->d_fmask);
-    c->d_fmask = nullptr;
-    if (c->d_fsum) (void)hipFree(c->d_fsum);
-    c->d_fsum = nullptr;
-    if (c->tier2_mask) {
-        HIPCHK(c, hipMalloc(&c->d_fmask, (size_t)cap * c->nx * (c->ny / 64) * sizeof(uint64_t)));
-        HIPCHK(c, hipMalloc(&c->d_fsum, (size_t)cap * sizeof(uint64_t)));
-    }
-    if (c->d_status) (void)hipFree(c->d_status);
-    c->d_status = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_status, cap));
-    if (c->d_noise) (void)hipFree(c->d_noise);
-    c->d_noise = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_noise, cap * 4 * sizeof(double)));
-    if (c->d_t2acc) (void)hipFree(c->d_t2acc);
-    c->d_t2acc = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_t2acc, cap * sizeof(T2Acc)));
-    HIPCHK(c, hipMemset(c->d_t2acc, 0, cap * sizeof(T2Acc)));   // tier 2 leaves it zero
-    if (c->d_skeys) (void)hipFree(c->d_skeys);
-    if (c->d_sidx) (void)hipFree(c->d_sidx);
-    if (c->d_stemp) (void)hipFree(c->d_stemp);
-    c->d_skeys = nullptr;
-    c->d_sidx = nullptr;
-    c->d_stemp = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_skeys, 2 * cap * sizeof(uint64_t)));
-    HIPCHK(c, hipMalloc(&c->d_sidx, 2 * cap * sizeof(int32_t)));
-    c->stemp_bytes = sort_temp_bytes(cap);
-    HIPCHK(c, hipMalloc(&c->d_stemp, c->stemp_bytes ? c->stemp_bytes : 16));
-    c->cap = cap;
-    return PDEVAL_OK;
+    a.kc = c->d_kc;
+    a.kc2 = c->d_kc ? c->d_kc + 4 * (size_t)c->n_pts : nullptr;
+    a.ptab = c->d_ptab;
+    a.n_ref = c->n_ref;
 }
 
 // dynamic LDS of one block: waves x (MAXD-1) stack slots x jet x 64 lanes (<= 160 KiB/CU)
@@ -924,36 +850,25 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     // checks every header); the kernels of the lists only deeper programs reach are skipped --
     // they would read a zero count and exit (what a small batch mostly pays for is launches)
     auto mark = [&](int k) {
-        if (c->timing) (void)hipEventRecord(c->ev[k], s);
+        if (c->timing) (void)hipEventRecord(c->ev.e[k], s);
     };
     KernelArgs a{};
     a.ops = d_ops;
     a.offsets = d_off;
     a.n_words = n_words;
     a.n = n;
-    for (int k = 0; k < 4; ++k) {
-        a.ref_x[k] = c->ref_x[k];
-        a.ref_y[k] = c->ref_y[k];
-        a.ref_xd[k] = c->ref_xd[k];
-        a.ref_yd[k] = c->ref_yd[k];
-    }
-    for (int k = 0; k < 16; ++k) a.kc_ref[k] = c->kc_ref[k];
-    copy_constants(c, a);
+    ctx_args(c, a);
     a.gx = c->d_gx;
     a.gy = c->d_gy;
     a.nx = c->nx;
     a.ny = c->ny;
-    a.kc = c->d_kc;
-    a.kc2 = c->d_kc ? c->d_kc + 4 * (size_t)c->n_pts : nullptr;
-    a.ptab = c->d_ptab;
-    a.n_ref = c->n_ref;
     a.n_pts = c->n_pts;
     for (int f = 0; f < PDEVAL_FP_N; ++f) a.fp_pts[f] = c->fp_pts[f];
     a.prm = prm;
     a.out = o;
     // the double-double tier reads the final classes: keep them even if the caller does not
-    if (!a.out.status) a.out.status = c->d_status;
-    a.list_capacity = c->cap;
+    if (!a.out.status) a.out.status = c->scr.status;
+    a.list_capacity = c->scr.cap;
     int32_t* const cnt = c->d_counts;
     // (a kernel, not hipMemsetAsync: captured into the small-batch graphs, a memset node was
     // seen to leave these counters unzeroed on replay -- the stale counts of an earlier, larger
@@ -977,13 +892,13 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     // stack appended to `out`, tier-1 failures to `esc`
     auto follow = [&](int in, int out, int esc) {
         KernelArgs b = a;
-        b.list = c->d_list[in];
+        b.list = c->scr.list[in];
         b.list_count = cnt + in;
-        b.defer_list = out >= 0 ? c->d_list[out] : nullptr;
+        b.defer_list = out >= 0 ? c->scr.list[out] : nullptr;
         b.defer_count = out >= 0 ? cnt + out : nullptr;
-        b.cplx_list = FF ? c->d_list[L_CPLX] : nullptr;   // real passes: not real at p* -> complex
+        b.cplx_list = FF ? c->scr.list[L_CPLX] : nullptr;   // real passes: not real at p* -> complex
         b.cplx_count = cnt + L_CPLX;
-        b.esc_list = c->d_list[esc];
+        b.esc_list = c->scr.list[esc];
         b.esc_count = cnt + esc;
         return b;
     };
@@ -991,40 +906,40 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     const unsigned pgrid = (unsigned)std::min<int64_t>(std::max<int64_t>(4 * blocks, n * lparts), 8192);
     // list-driven point kernels (one candidate per lane): enough blocks for the rare lists
     const unsigned lgrid = (unsigned)std::min<int64_t>((n + 63) / 64, 2048);
-    a.defer_list = c->d_list[L_DEFER];
+    a.defer_list = c->scr.list[L_DEFER];
     a.defer_count = cnt + L_DEFER;
-    a.cplx_list = FF ? c->d_list[L_CPLX] : nullptr;
+    a.cplx_list = FF ? c->scr.list[L_CPLX] : nullptr;
     a.cplx_count = cnt + L_CPLX;
-    a.esc_list = c->d_list[L_ESC];
+    a.esc_list = c->scr.list[L_ESC];
     a.esc_count = cnt + L_ESC;
-    a.pstate = c->d_pstate;
-    a.ddps = c->d_ddps;
-    a.dd_res = c->d_dd_res;
-    a.dd_q = c->d_dd_q;
+    a.pstate = c->scr.pstate;
+    a.ddps = c->scr.ddps;
+    a.dd_res = c->scr.dd_res;
+    a.dd_q = c->scr.dd_q;
     a.dd_spec = 0;   // (set in launch_all when the early tier runs)
-    a.pdeep_list = c->d_list[L_PDEEP];
+    a.pdeep_list = c->scr.list[L_PDEEP];
     a.pdeep_count = cnt + L_PDEEP;
-    a.noise_ref = c->d_noise;
-    a.t2acc = c->d_t2acc;
-    a.dec = c->d_dec;
-    a.hoist = c->nx <= 64 ? c->d_hoist : nullptr;   // (one grid row per lane)
-    a.hoist_own = c->hoist_slots ? c->d_hoist_own : nullptr;
+    a.noise_ref = c->scr.noise;
+    a.t2acc = (T2Acc*)c->scr.t2acc.p;
+    a.dec = c->scr.dec;
+    a.hoist = c->nx <= 64 ? c->scr.hoist.p : nullptr;   // (one grid row per lane)
+    a.hoist_own = c->scr.hoist_own;   // (none: one slot per candidate, ScratchCfg::hoist_slots)
     a.hoist_pool = pd::kHoistPool;
-    a.hseg = a.hoist && c->hoist_sub ? c->d_hseg : nullptr;
-    a.fmask = c->d_fmask;
-    a.fsum = c->d_fsum;
+    a.hseg = a.hoist && c->hoist_sub ? c->scr.hseg : nullptr;
+    a.fmask = c->scr.fmask;
+    a.fsum = c->scr.fsum;
     // ---- the point stage (pdeval_point.h), decided for every candidate before the grid
     // pass 0: real programs of stack <= 2, one candidate per lane; deeper ones -> L_PDEEP,
     // complex-valued ones -> L_CPLX.  Lanes take the candidates sorted by opcode sequence
     // (pdeval_sort.hip; the sort is part of pass 0's time)
     mark(0);
     if (c->sort && n > 1) {
-        const int rc = sort_batch(d_ops, d_off, n_words, n, c->d_skeys, c->d_sidx, c->d_stemp, c->stemp_bytes, s);
+        const int rc = sort_batch(d_ops, d_off, n_words, n, c->scr.skeys, c->scr.sidx, c->scr.stemp, c->scr.stemp_bytes, s);
         if (rc != 0) {
             c->err = std::string("shape sort: ") + hipGetErrorString((hipError_t)rc);
             return PDEVAL_ERR_HIP;
         }
-        a.perm = c->d_sidx + n;
+        a.perm = c->scr.sidx + n;
     }
     hipLaunchKernelGGL((point_kernel<PROB>), dim3((unsigned)((n + 255) / 256)), dim3(256),
                        (size_t)4 * 2 * nc(K) * 64 * sizeof(double), s, a);
@@ -1044,11 +959,11 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     // the double-double lists: early = L_DD / L_DDC / L_DD8, late = L_DDL / L_DDLC / L_DDL8
     auto dd_lists = [&](int l0, int lc, int l8) {
         KernelArgs b = a;
-        b.defer_list = c->d_list[l0];
+        b.defer_list = c->scr.list[l0];
         b.defer_count = cnt + l0;
-        b.cplx_list = c->d_list[lc];   // (Kerr: never appended to, count 0)
+        b.cplx_list = c->scr.list[lc];   // (Kerr: never appended to, count 0)
         b.cplx_count = cnt + lc;
-        b.esc_list = c->d_list[l8];
+        b.esc_list = c->scr.list[l8];
         b.esc_count = cnt + l8;
         return b;
     };
@@ -1066,13 +981,13 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
         // on the side stream beside the grid passes (classes to ddps, applied after the grid)
         hipLaunchKernelGGL((dd_collect_kernel<PROB, DD_EARLY>), dim3(cgrid), dim3(256), 0, s, dd_lists(L_DD, L_DDC, L_DD8));
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_fork, s));
-        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+        HIPCHK(c, hipEventRecord(c->ev_fj.e[0], s));
+        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fj.e[0], 0));
         launch_dd_point(PROB, 0, lgrid, c->side, follow(L_DD, -1, L_ESC), true);
         if (dmax > 2) launch_dd_point(PROB, 1, lgrid, c->side, follow(L_DD8, -1, L_ESC), true);
         if constexpr (FF) launch_dd_point(PROB, 2, lgrid, c->side, follow(L_DDC, -1, L_ESC), true);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(c->ev_join, c->side));
+        HIPCHK(c, hipEventRecord(c->ev_fj.e[1], c->side));
     }
     // ---- the grid stage
     // pass 1: programs whose stack fits 2 jets (99 % of force-free depth 4), one wave per
@@ -1080,7 +995,7 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     mark(2);
     launch_decode(PROB, n, s, a);   // (part of pass 1's time)
     HIPCHK(c, hipGetLastError());
-    launch_grid(PROB, n, s, a, c->d_list[L_SLOW], cnt + L_SLOW);
+    launch_grid(PROB, n, s, a, c->scr.list[L_SLOW], cnt + L_SLOW);
     HIPCHK(c, hipGetLastError());
     // what the lean pass did not take (normally nothing): the generic kernel, same pass slot
     hipLaunchKernelGGL((validate_kernel<PROB, double, 2, true>), dim3((unsigned)std::min<int64_t>(blocks, 256)),
@@ -1090,9 +1005,9 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     // slots); what it does not take, the generic stack-3 kernel
     mark(3);
     if (dmax > 2) {
-        hipLaunchKernelGGL(sanitize_list_kernel, dim3(64), dim3(256), 0, s, c->d_list[L_DEFER], cnt + L_DEFER, c->cap, n,
+        hipLaunchKernelGGL(sanitize_list_kernel, dim3(64), dim3(256), 0, s, c->scr.list[L_DEFER], cnt + L_DEFER, c->scr.cap, n,
                            a.errw, (uint32_t)ERRW_GRID_LIST);
-        launch_grid_list(PROB, pgrid, s, queue(follow(L_DEFER, L_DEFER2, L_ESC), Q_PASS2), c->d_list[L_SLOW2],
+        launch_grid_list(PROB, pgrid, s, queue(follow(L_DEFER, L_DEFER2, L_ESC), Q_PASS2), c->scr.list[L_SLOW2],
                          cnt + L_SLOW2, lparts);
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL((validate_kernel<PROB, double, 3, true>), dim3((unsigned)std::min<int64_t>(blocks, 256)),
@@ -1121,9 +1036,9 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
         // the lean interpreter in complex arithmetic over the decoded programs; what it does not
         // take (point stage undecided, malformed) the generic complex kernel drains
         if (c->lean_cplx) {
-            hipLaunchKernelGGL(sanitize_list_kernel, dim3(64), dim3(256), 0, s, c->d_list[L_CPLX], cnt + L_CPLX, c->cap,
+            hipLaunchKernelGGL(sanitize_list_kernel, dim3(64), dim3(256), 0, s, c->scr.list[L_CPLX], cnt + L_CPLX, c->scr.cap,
                                n, a.errw, (uint32_t)ERRW_CPLX);
-            launch_grid_cplx(pgrid, s, queue(follow(L_CPLX, L_CPLX_DEEP, L_ESC_C), Q_CPLX), c->d_list[L_SLOW_C],
+            launch_grid_cplx(pgrid, s, queue(follow(L_CPLX, L_CPLX_DEEP, L_ESC_C), Q_CPLX), c->scr.list[L_SLOW_C],
                              cnt + L_SLOW_C, lparts);
             HIPCHK(c, hipGetLastError());
             hipLaunchKernelGGL((validate_kernel<PROB, cplx, 2, true>), dim3((unsigned)std::min<int64_t>(blocks, 256)),
@@ -1190,7 +1105,7 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     if (early) {
         // join the side stream; the late lists (provisional point passes the grid classes
         // now make relevant), then the early tier's classes applied to the final grid classes
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0));
+        HIPCHK(c, hipStreamWaitEvent(s, c->ev_fj.e[1], 0));
         hipLaunchKernelGGL((dd_collect_kernel<PROB, DD_LATE>), dim3(cgrid), dim3(256), 0, s, dd_lists(L_DDL, L_DDLC, L_DDL8));
         HIPCHK(c, hipGetLastError());
         launch_dd_point(PROB, 0, lgrid, s, follow(L_DDL, -1, L_ESC));
@@ -1232,10 +1147,8 @@ static int validate_device(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words,
     pdeval_params prm;
     if (params) prm = *params;
     else pdeval_default_params(c->problem, &prm);
-    int rc = ensure_scratch(c, n);
-    if (rc) return rc;
-    rc = ensure_dec(c, n_words);
-    if (rc) return rc;
+    // (grown when a batch outgrows it; never inside an already-sized call)
+    HIPCHK(c, c->scr.reserve(n, n_words, c->cfg, c->buf_epoch));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     if (zero_bits && d_out->verdict_bits)
         HIPCHK(c, hipMemsetAsync(d_out->verdict_bits, 0, ((n + 31) / 32) * 4, s));
@@ -1288,8 +1201,8 @@ static int check_errw(pdeval_ctx* c, uint32_t w, const char* path = "direct", in
                   "device work-list check failed (kernel families 0x%x; 0x100: no free hoist slot): a list entry "
                   "outside the batch [%s n=%lld "
                   "captured=%d cap=%lld epoch=%llu graphs=%zu counts=",
-                  (unsigned)w, path, (long long)n, captured, (long long)c->cap, (unsigned long long)c->buf_epoch,
-                  c->graphs.size());
+                  (unsigned)w, path, (long long)n, captured, (long long)c->scr.cap, (unsigned long long)c->buf_epoch,
+                  c->graphs.m.size());
     c->err = std::string(buf) + cnt + "]";
     return PDEVAL_ERR_HIP;
 }
@@ -1312,42 +1225,39 @@ static int64_t outbuf_layout(const pdeval_ctx* c, int64_t n, pdeval_outputs* d) 
     return need;
 }
 
+// the eight outputs of a host call: the caller's array (NULL: not asked for), its place in the
+// device output block d (outbuf_layout) and its size in bytes
+struct OutCopy {
+    void* h;
+    const void* dv;
+    size_t bytes;
+};
+static std::array<OutCopy, 8> out_copies(const pdeval_ctx* c, const pdeval_outputs& h, const pdeval_outputs& d, int64_t n) {
+    const size_t m = (size_t)n;
+    return {{{h.verdict_bits, d.verdict_bits, (m + 7) / 8}, {h.status, d.status, m}, {h.q_ref, d.q_ref, 8 * m},
+             {h.q_grid, d.q_grid, 8 * m}, {h.res_ref, d.res_ref, 8 * m * c->n_ref},
+             {h.fingerprint, d.fingerprint, 8 * m * PDEVAL_FP_N}, {h.n_bad, d.n_bad, 4 * m},
+             {h.n_nonfinite, d.n_nonfinite, 4 * m}}};
+}
+
+// the host path's device buffers: room for a batch's program words, its offsets and `out_bytes`
+// of outputs
+static int ensure_host_bufs(pdeval_ctx* c, int64_t n_words, int64_t n_off, int64_t out_bytes) {
+    HIPCHK(c, c->d_ops.replace(n_words, c->buf_epoch));
+    HIPCHK(c, c->d_off.replace(n_off, c->buf_epoch));
+    HIPCHK(c, c->d_outbuf.replace(out_bytes, c->buf_epoch));
+    return PDEVAL_OK;
+}
+
 static int validate_small(pdeval_ctx* c, const int32_t* ops, int64_t n_words, const int64_t* offsets, int64_t n,
                           const pdeval_params* params, pdeval_outputs* out, int dmax) {
     if (n_words > kSmallWords) return kGraphFallback;
     // fixed-capacity buffers (growing them drops every captured graph)
-    if (c->hcap_words < kSmallWords || c->hcap_n < PD_GRAPH_MAX_N + 1) {
-        ++c->buf_epoch;
-        const int64_t w = std::max<int64_t>(kSmallWords, c->hcap_words);
-        const int64_t m = std::max<int64_t>(PD_GRAPH_MAX_N + 1, c->hcap_n);
-        if (c->d_ops) (void)hipFree(c->d_ops);
-        if (c->d_off) (void)hipFree(c->d_off);
-        c->d_ops = nullptr;
-        c->d_off = nullptr;
-        c->hcap_words = c->hcap_n = 0;
-        HIPCHK(c, hipMalloc(&c->d_ops, w * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(&c->d_off, m * sizeof(int64_t)));
-        c->hcap_words = w;
-        c->hcap_n = m;
-    }
     const int64_t need_max = outbuf_layout(c, PD_GRAPH_MAX_N, nullptr);
-    if (c->outbuf_bytes < need_max) {
-        ++c->buf_epoch;
-        if (c->d_outbuf) (void)hipFree(c->d_outbuf);
-        c->d_outbuf = nullptr;
-        c->outbuf_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->d_outbuf, need_max));
-        c->outbuf_bytes = need_max;
-    }
-    int rc = ensure_scratch(c, n);
-    if (rc) return rc;
-    rc = ensure_dec(c, c->hcap_words);
-    if (rc) return rc;
+    if (int rc = ensure_host_bufs(c, kSmallWords, PD_GRAPH_MAX_N + 1, need_max)) return rc;
+    HIPCHK(c, c->scr.reserve(n, c->d_ops.cap, c->cfg, c->buf_epoch));
     const size_t in_bytes = kSmallWords * 4 + (PD_GRAPH_MAX_N + 1) * 8;
-    if (!c->h_stage) {
-        HIPCHK(c, hipHostMalloc((void**)&c->h_stage, in_bytes + need_max + 16, hipHostMallocDefault));
-        c->h_stage_bytes = in_bytes + need_max + 16;
-    }
+    if (!c->h_stage.p) HIPCHK(c, c->h_stage.alloc(in_bytes + need_max + 16));
     pdeval_params prm;
     if (params) prm = *params;
     else pdeval_default_params(c->problem, &prm);
@@ -1364,19 +1274,17 @@ static int validate_small(pdeval_ctx* c, const int32_t* ops, int64_t n_words, co
     pdeval_outputs d{};
     const int64_t need = outbuf_layout(c, n, &d);
     hipStream_t s = c->stream;
-    auto it = c->graphs.find(key);
-    if (it != c->graphs.end() && it->second.epoch != c->buf_epoch) {
+    auto& graphs = c->graphs.m;
+    auto it = graphs.find(key);
+    if (it != graphs.end() && it->second.epoch != c->buf_epoch) {
         (void)hipGraphExecDestroy(it->second.exec);
-        c->graphs.erase(it);
-        it = c->graphs.end();
+        graphs.erase(it);
+        it = graphs.end();
     }
     int fresh = 0;
-    if (it == c->graphs.end()) {
+    if (it == graphs.end()) {
         fresh = 1;
-        if (c->graphs.size() >= 256) {   // bounded cache
-            for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.second.exec);
-            c->graphs.clear();
-        }
+        if (graphs.size() >= 256) c->graphs.clear();   // bounded cache
         hipGraph_t g = nullptr;
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return kGraphFallback;
         int lrc = PDEVAL_OK;
@@ -1384,8 +1292,8 @@ static int validate_small(pdeval_ctx* c, const int32_t* ops, int64_t n_words, co
         if (hipGetLastError() != hipSuccess) lrc = PDEVAL_ERR_HIP;
         if (lrc == PDEVAL_OK)
             lrc = c->problem == PDEVAL_PROBLEM_FORCE_FREE
-                      ? launch_all<PDEVAL_PROBLEM_FORCE_FREE>(c, c->d_ops, c->hcap_words, c->d_off, n, prm, d, s, dmax)
-                      : launch_all<PDEVAL_PROBLEM_KERR>(c, c->d_ops, c->hcap_words, c->d_off, n, prm, d, s, dmax);
+                      ? launch_all<PDEVAL_PROBLEM_FORCE_FREE>(c, c->d_ops, c->d_ops.cap, c->d_off, n, prm, d, s, dmax)
+                      : launch_all<PDEVAL_PROBLEM_KERR>(c, c->d_ops, c->d_ops.cap, c->d_off, n, prm, d, s, dmax);
         const hipError_t ee = hipStreamEndCapture(s, &g);
         hipGraphExec_t exec = nullptr;
         if (lrc != PDEVAL_OK || ee != hipSuccess || !g || hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) != hipSuccess) {
@@ -1395,10 +1303,10 @@ static int validate_small(pdeval_ctx* c, const int32_t* ops, int64_t n_words, co
             return kGraphFallback;
         }
         (void)hipGraphDestroy(g);
-        it = c->graphs.emplace(key, pdeval_ctx::GraphEntry{exec, c->buf_epoch}).first;
+        it = graphs.emplace(key, Graphs::Entry{exec, c->buf_epoch}).first;
     }
-    uint8_t* hin = c->h_stage;
-    uint8_t* hout = c->h_stage + in_bytes;
+    uint8_t* hin = c->h_stage.p;
+    uint8_t* hout = hin + in_bytes;
     std::memcpy(hin, offsets, (n + 1) * sizeof(int64_t));
     std::memcpy(hin + (PD_GRAPH_MAX_N + 1) * 8, ops, n_words * sizeof(int32_t));
     HIPCHK(c, hipMemcpyAsync(c->d_off, hin, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -1406,21 +1314,12 @@ static int validate_small(pdeval_ctx* c, const int32_t* ops, int64_t n_words, co
                              hipMemcpyHostToDevice, s));
     HIPCHK(c, hipGraphLaunch(it->second.exec, s));
     HIPCHK(c, hipMemcpyAsync(hout, c->d_outbuf, need, hipMemcpyDeviceToHost, s));
-    uint32_t* herr = reinterpret_cast<uint32_t*>(c->h_stage + in_bytes + need_max);
+    uint32_t* herr = reinterpret_cast<uint32_t*>(hout + need_max);
     HIPCHK(c, hipMemcpyAsync(herr, c->d_counts + PD_N_LISTS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (int erc = check_errw(c, *herr, "graph", n, fresh)) return erc;
-    auto take = [&](void* h, const void* dv, size_t bytes) {
+    for (const auto& [h, dv, bytes] : out_copies(c, *out, d, n))
         if (h) std::memcpy(h, hout + ((const uint8_t*)dv - c->d_outbuf), bytes);
-    };
-    take(out->verdict_bits, d.verdict_bits, (n + 7) / 8);
-    take(out->status, d.status, n);
-    take(out->q_ref, d.q_ref, 8 * n);
-    take(out->q_grid, d.q_grid, 8 * n);
-    take(out->res_ref, d.res_ref, 8 * n * c->n_ref);
-    take(out->fingerprint, d.fingerprint, 8 * n * PDEVAL_FP_N);
-    take(out->n_bad, d.n_bad, 4 * n);
-    take(out->n_nonfinite, d.n_nonfinite, 4 * n);
     return PDEVAL_OK;
 }
 
@@ -1459,66 +1358,18 @@ extern "C" int pdeval_validate_batch(pdeval_ctx* c, const int32_t* ops, int64_t 
         const int rc = validate_small(c, ops, n_words, offsets, n, params, out, dmax);
         if (rc != kGraphFallback) return rc;
     }
-    if (n_words > c->hcap_words) {
-        ++c->buf_epoch;
-        if (c->d_ops) (void)hipFree(c->d_ops);
-        c->d_ops = nullptr;
-        c->hcap_words = 0;
-        HIPCHK(c, hipMalloc(&c->d_ops, n_words * sizeof(int32_t)));
-        c->hcap_words = n_words;
-    }
-    if (n + 1 > c->hcap_n) {
-        ++c->buf_epoch;
-        if (c->d_off) (void)hipFree(c->d_off);
-        c->d_off = nullptr;
-        c->hcap_n = 0;
-        HIPCHK(c, hipMalloc(&c->d_off, (n + 1) * sizeof(int64_t)));
-        c->hcap_n = n + 1;
-    }
-    // device output block
-    const int64_t nb = ((n + 31) / 32) * 4;
-    const int64_t sz_bits = (nb + 15) / 16 * 16, sz_st = (n + 15) / 16 * 16;
-    const int64_t need = sz_bits + sz_st + 8 * n * (3 + c->n_ref + PDEVAL_FP_N) + 8 * n * 2;
-    if (need > c->outbuf_bytes) {
-        ++c->buf_epoch;
-        if (c->d_outbuf) (void)hipFree(c->d_outbuf);
-        c->d_outbuf = nullptr;
-        c->outbuf_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->d_outbuf, need));
-        c->outbuf_bytes = need;
-    }
-    uint8_t* p = c->d_outbuf;
+    if (int rc = ensure_host_bufs(c, n_words, n + 1, outbuf_layout(c, n, nullptr))) return rc;
     pdeval_outputs d{};
-    d.verdict_bits = p; p += sz_bits;
-    d.status = p; p += sz_st;
-    d.q_ref = (double*)p; p += 8 * n;
-    d.q_grid = (double*)p; p += 8 * n;
-    d.res_ref = (double*)p; p += 8 * n * c->n_ref;
-    d.fingerprint = (double*)p; p += 8 * n * PDEVAL_FP_N;
-    d.n_bad = (int32_t*)p; p += 4 * n;
-    d.n_nonfinite = (int32_t*)p; p += 4 * n;
+    outbuf_layout(c, n, &d);
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->d_ops, ops, n_words * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->d_off, offsets, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     int rc = validate_device(c, c->d_ops, n_words, c->d_off, n, params, &d, s, 1, dmax);
     if (rc) return rc;
-    auto dl = [&](void* h, const void* dv, size_t bytes) -> int {
+    for (const auto& [h, dv, bytes] : out_copies(c, *out, d, n))
         if (h) HIPCHK(c, hipMemcpyAsync(h, dv, bytes, hipMemcpyDeviceToHost, s));
-        return PDEVAL_OK;
-    };
-    if ((rc = dl(out->verdict_bits, d.verdict_bits, (n + 7) / 8))) return rc;
-    if ((rc = dl(out->status, d.status, n))) return rc;
-    if ((rc = dl(out->q_ref, d.q_ref, 8 * n))) return rc;
-    if ((rc = dl(out->q_grid, d.q_grid, 8 * n))) return rc;
-    if ((rc = dl(out->res_ref, d.res_ref, 8 * n * c->n_ref))) return rc;
-    if ((rc = dl(out->fingerprint, d.fingerprint, 8 * n * PDEVAL_FP_N))) return rc;
-    if ((rc = dl(out->n_bad, d.n_bad, 4 * n))) return rc;
-    if ((rc = dl(out->n_nonfinite, d.n_nonfinite, 4 * n))) return rc;
-    uint32_t* herr = reinterpret_cast<uint32_t*>(c->h_errw);
-    if (!herr) {
-        HIPCHK(c, hipHostMalloc((void**)&c->h_errw, 16, hipHostMallocDefault));
-        herr = reinterpret_cast<uint32_t*>(c->h_errw);
-    }
+    if (!c->h_errw.p) HIPCHK(c, c->h_errw.alloc(16));
+    uint32_t* herr = reinterpret_cast<uint32_t*>(c->h_errw.p);
     HIPCHK(c, hipMemcpyAsync(herr, c->d_counts + PD_N_LISTS, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return check_errw(c, *herr, "direct", n);
@@ -1527,8 +1378,7 @@ extern "C" int pdeval_validate_batch(pdeval_ctx* c, const int32_t* ops, int64_t 
 extern "C" int pdeval_set_timing(pdeval_ctx* c, int enable) {
     if (!c) return PDEVAL_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (enable && !c->ev[0])
-        for (hipEvent_t& e : c->ev) HIPCHK(c, hipEventCreate(&e));
+    if (enable && !c->ev.e[0]) HIPCHK(c, c->ev.create(hipEventDefault));
     c->timing = enable != 0;
     c->ev_recorded = 0;
     return PDEVAL_OK;
@@ -1541,10 +1391,10 @@ extern "C" int pdeval_pass_times(pdeval_ctx* c, float* ms, int max_passes, const
         return PDEVAL_ERR_ARG;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipEventSynchronize(c->ev[PDEVAL_N_PASSES]));
+    HIPCHK(c, hipEventSynchronize(c->ev.e[PDEVAL_N_PASSES]));
     const int n = max_passes < PDEVAL_N_PASSES ? max_passes : PDEVAL_N_PASSES;
     for (int k = 0; k < n; ++k) {
-        HIPCHK(c, hipEventElapsedTime(&ms[k], c->ev[k], c->ev[k + 1]));
+        HIPCHK(c, hipEventElapsedTime(&ms[k], c->ev.e[k], c->ev.e[k + 1]));
         if (names) names[k] = kPassNames[k];
     }
     return PDEVAL_OK;
@@ -1573,29 +1423,24 @@ extern "C" int pdeval_eval_points(pdeval_ctx* c, const int32_t* prog, int64_t n_
         return PDEVAL_ERR_ARG;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    int32_t* d_prog = nullptr;
-    double *d_x = nullptr, *d_y = nullptr, *d_out = nullptr, *d_jets = nullptr;
+    DevBuf<int32_t> d_prog;
+    DevBuf<double> d_x, d_y, d_out, d_jets;   // (freed on return)
     const size_t jet_bytes = (size_t)n_pts * 2 * 15 * sizeof(double);
-    auto cleanup = [&]() {
-        for (void* q : {(void*)d_prog, (void*)d_x, (void*)d_y, (void*)d_out, (void*)d_jets})
-            if (q) (void)hipFree(q);
-    };
-    hipError_t e = hipSuccess;
-    if ((e = hipMalloc(&d_prog, n_words * 4)) == hipSuccess && (e = hipMalloc(&d_x, n_pts * 8)) == hipSuccess &&
-        (e = hipMalloc(&d_y, n_pts * 8)) == hipSuccess && (e = hipMalloc(&d_out, n_pts * 32)) == hipSuccess &&
-        (e = hipMemcpy(d_prog, prog, n_words * 4, hipMemcpyHostToDevice)) == hipSuccess &&
+    hipError_t e = d_prog.reserve(n_words) && d_x.reserve(n_pts) && d_y.reserve(n_pts) && d_out.reserve(4 * n_pts) &&
+                           (!jets || d_jets.reserve(2 * 15 * n_pts))
+                       ? hipSuccess
+                       : hipErrorOutOfMemory;
+    if (e == hipSuccess && (e = hipMemcpy(d_prog, prog, n_words * 4, hipMemcpyHostToDevice)) == hipSuccess &&
         (e = hipMemcpy(d_x, xs, n_pts * 8, hipMemcpyHostToDevice)) == hipSuccess &&
-        (e = hipMemcpy(d_y, ys, n_pts * 8, hipMemcpyHostToDevice)) == hipSuccess &&
-        (!jets || (e = hipMalloc(&d_jets, jet_bytes)) == hipSuccess)) {
+        (e = hipMemcpy(d_y, ys, n_pts * 8, hipMemcpyHostToDevice)) == hipSuccess) {
         constexpr int K = 4, MAXD = PDEVAL_MAX_STACK;
         hipLaunchKernelGGL((eval_points_kernel<PDEVAL_PROBLEM_FORCE_FREE, MAXD>), dim3((n_pts + 63) / 64), dim3(64),
-                           (tier2_lds<double, K, MAXD>()), c->stream, d_prog, (int)n_words, d_x, d_y,
-                           (const double*)nullptr, n_pts, tier2, d_out, d_jets);
+                           (tier2_lds<double, K, MAXD>()), c->stream, d_prog.p, (int)n_words, d_x.p, d_y.p,
+                           (const double*)nullptr, n_pts, tier2, d_out.p, d_jets.p);
         if ((e = hipGetLastError()) == hipSuccess && (e = hipStreamSynchronize(c->stream)) == hipSuccess)
             e = hipMemcpy(out, d_out, n_pts * 32, hipMemcpyDeviceToHost);
         if (e == hipSuccess && jets) e = hipMemcpy(jets, d_jets, jet_bytes, hipMemcpyDeviceToHost);
     }
-    cleanup();
     if (e != hipSuccess) {
         c->err = std::string("pdeval_eval_points: ") + hipGetErrorString(e);
         return PDEVAL_ERR_HIP;
@@ -1604,14 +1449,14 @@ extern "C" int pdeval_eval_points(pdeval_ctx* c, const int32_t* prog, int64_t n_
 }
 
 extern "C" int pdeval_point_states(pdeval_ctx* c, uint8_t* out, int64_t n) {
-    if (!c || !out || n < 0 || n > c->cap) {
+    if (!c || !out || n < 0 || n > c->scr.cap) {
         if (c) c->err = "pdeval_point_states: bad argument";
         return PDEVAL_ERR_ARG;
     }
     if (n == 0) return PDEVAL_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, c->d_pstate, n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->scr.pstate, n, hipMemcpyDeviceToHost));
     return PDEVAL_OK;
 }
 
@@ -1631,33 +1476,18 @@ extern "C" int pdeval_point_eval(pdeval_ctx* c, const int32_t* prog, int64_t n_w
     pdeval_params prm;
     pdeval_default_params(c->problem, &prm);
     KernelArgs a{};
-    for (int k = 0; k < 4; ++k) {
-        a.ref_x[k] = c->ref_x[k];
-        a.ref_y[k] = c->ref_y[k];
-        a.ref_xd[k] = c->ref_xd[k];
-        a.ref_yd[k] = c->ref_yd[k];
-    }
-    for (int k = 0; k < 16; ++k) a.kc_ref[k] = c->kc_ref[k];
-    copy_constants(c, a);
-    a.kc = c->d_kc;
-    a.kc2 = c->d_kc ? c->d_kc + 4 * (size_t)c->n_pts : nullptr;
-    a.ptab = c->d_ptab;
-    a.n_ref = c->n_ref;
+    ctx_args(c, a);
     a.prm = prm;
-    int32_t* d_prog = nullptr;
-    double* d_out = nullptr;
-    uint8_t* d_st = nullptr;
-    hipError_t e = hipSuccess;
-    if ((e = hipMalloc(&d_prog, n_words * 4)) == hipSuccess && (e = hipMalloc(&d_out, 6 * 4 * 8)) == hipSuccess &&
-        (e = hipMalloc(&d_st, 1)) == hipSuccess &&
-        (e = hipMemcpy(d_prog, prog, n_words * 4, hipMemcpyHostToDevice)) == hipSuccess) {
+    DevBuf<int32_t> d_prog;
+    DevBuf<double> d_out;
+    DevBuf<uint8_t> d_st;   // (freed on return)
+    hipError_t e = d_prog.reserve(n_words) && d_out.reserve(6 * 4) && d_st.reserve(1) ? hipSuccess : hipErrorOutOfMemory;
+    if (e == hipSuccess && (e = hipMemcpy(d_prog, prog, n_words * 4, hipMemcpyHostToDevice)) == hipSuccess) {
         launch_point_eval(c->problem, tier, c->stream, a, d_prog, (int)n_words, d_out, d_st);
         if ((e = hipGetLastError()) == hipSuccess && (e = hipStreamSynchronize(c->stream)) == hipSuccess &&
             (e = hipMemcpy(out, d_out, 6 * c->n_ref * 8, hipMemcpyDeviceToHost)) == hipSuccess)
             e = hipMemcpy(state, d_st, 1, hipMemcpyDeviceToHost);
     }
-    for (void* q : {(void*)d_prog, (void*)d_out, (void*)d_st})
-        if (q) (void)hipFree(q);
     if (e != hipSuccess) {
         c->err = std::string("pdeval_point_eval: ") + hipGetErrorString(e);
         return PDEVAL_ERR_HIP;

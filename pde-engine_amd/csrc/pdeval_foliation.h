@@ -12,12 +12,15 @@
 //
 // This header holds the per-point code of the kernels and the leader round, which also compile
 // for the host under -DPD_HOST_SIM (tests/hostsim/sim_foliation.cpp, sim_foliation_field.cpp),
-// the kernels' argument blocks, the launchers and the owning device buffer of the entry points.
+// the kernels' argument blocks and the launchers.
 #pragma once
 #include <utility>
 #include <vector>
 
 #include "pdeval_kernels.h"
+#ifndef PD_HOST_SIM
+#include "pdeval_devbuf.h"   // DevBuf<T>, the owning device buffer of the entry points
+#endif
 
 struct pdeval_ctx;
 
@@ -322,37 +325,6 @@ struct FolKindArgs {
 void launch_fol_kind(const FolKindArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- host side
-// An owning device buffer of `cap` elements.  It grows by a new allocation and copies nothing
-// (the leader store's growth copies for itself and swaps the new block in); the destructor
-// frees, on the device that is current then.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    int64_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { (void)hipFree(p); }
-    // room for n elements; false (the old block and capacity untouched, no HIP error left
-    // pending) when the allocation fails
-    bool reserve(int64_t n) {
-        if (n <= cap) return true;
-        T* q = nullptr;
-        if (hipMalloc((void**)&q, (size_t)n * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        (void)hipFree(p);
-        p = q;
-        cap = n;
-        return true;
-    }
-    void swap(DevBuf& o) {
-        std::swap(p, o.p);
-        std::swap(cap, o.cap);
-    }
-};
-
 // what the entry points (pdeval_foliation.hip, pdeval_fol_registry.hip) need of a context (pdeval.hip)
 struct FolCtx {
     int problem, device;

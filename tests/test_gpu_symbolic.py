@@ -316,6 +316,49 @@ def test_small_batch_graph_after_set_kerr_constants():
         direct.close()
 
 
+@pytest.mark.parametrize('problem, files', [('force_free', ('ff_d4_s2000.jsonl',)),
+                                            ('kerr_magnetosphere', ('kerr_evidence.jsonl',))])
+def test_graph_replay_across_scratch_growth(problem, files):
+    """One context through every way its buffers move: a 7-candidate host batch captures a graph,
+    a 1,500-candidate device-entry call grows the scratch past its 1,024-candidate and 4,096-word
+    minimums, a 5,000-candidate host batch grows it and the host path's buffers again, and the 7
+    follow each -- the smallest sizes on both sides of the 64-candidate graph limit, the minimums
+    and a second growth.  Every output of every step, and point_states(7) at the end, equals that
+    of a fresh PDEVAL_GRAPH=0 context given the same call alone, and the device error word stays
+    0 -- with the hoist slot pool (default) and with one slot per candidate (PDEVAL_HOIST_SLOTS=0),
+    whose slot buffer grows with the batch."""
+    from pdeval import problem_defs as P
+    from pdeval.workload import gather_programs
+    pd_ = P.get(problem)
+    strs = [r['expr'] for r in G.decided(G.ref_rows(*files))][:600]
+    ops, off, _ = P.compile_strings(pd_, strs)
+    calls = {n: gather_programs(ops, off, np.arange(n) % len(strs)) for n in (7, 1500, 5000)}
+    keys = ('status', 'verdict', 'q_ref', 'res_ref', 'q_grid', 'n_bad', 'n_nonfinite', 'fingerprint')
+    want = {}
+    for n in calls:   # the reference: each call alone on a fresh direct-path context, computed once
+        d = _ctx_with_env(pd_.problem_id, {'PDEVAL_GRAPH': '0'})
+        try:
+            want[n] = _device_outputs(d, *calls[n], d.n_ref) if n == 1500 else d.validate(*calls[n])
+            if n == 7:
+                want['pstate'] = d.point_states(7)
+            assert d.device_error() == 0
+        finally:
+            d.close()
+    for env in ({}, {'PDEVAL_HOIST_SLOTS': '0'}):
+        g = _ctx_with_env(pd_.problem_id, env)
+        try:
+            for step, n in enumerate((7, 1500, 7, 5000, 7)):
+                got = _device_outputs(g, *calls[n], g.n_ref) if n == 1500 else g.validate(*calls[n])
+                assert g.device_error() == 0, (env, step)
+                for k in keys:
+                    x, y = np.asarray(got[k]).ravel(), np.asarray(want[n][k]).ravel()
+                    assert np.array_equal(x, y, equal_nan=x.dtype.kind == 'f'), (env, step, n, k)
+            assert np.array_equal(g.point_states(7), want['pstate']), env
+            assert g.device_error() == 0, env
+        finally:
+            g.close()
+
+
 @pytest.mark.parametrize('n', [1023, 1024, 4096])
 def test_dd_early_split_equals_single_tier(n):
     """The double-double tier beside the grid (PDEVAL_DD_EARLY=1: the P0_DD lists on a side
