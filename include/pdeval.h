@@ -255,7 +255,7 @@ int pdeval_device_error(pdeval_ctx* ctx, uint32_t* word);
  * the launch stream (passes a problem does not run take 0 ms).  pdeval_pass_times waits for
  * the last event of the most recent call and writes min(max_passes, PDEVAL_N_PASSES)
  * durations in ms (and, if names != NULL, a static name per pass).                       */
-#define PDEVAL_N_PASSES 12
+#define PDEVAL_N_PASSES 13
 int pdeval_set_timing(pdeval_ctx* ctx, int enable);
 int pdeval_pass_times(pdeval_ctx* ctx, float* ms, int max_passes, const char** names);
 /* Work-list sizes of the most recent call (synchronizes the device): [0] deferred to the
@@ -264,7 +264,10 @@ int pdeval_pass_times(pdeval_ctx* ctx, float* ms, int max_passes, const char** n
  * [8] deep point pass (real, stack 3..8), [9] double-double point tier (real, stack <= 2),
  * [10] double-double point tier (complex), [11] double-double point tier (real, stack 3..8),
  * [12] complex tier 2, stack 5..8, [13] candidates the lean grid pass handed to the generic
- * stack-2 kernel (malformed or point-stage-undecided programs; normally 0).              */
+ * stack-2 kernel (malformed or point-stage-undecided programs; normally 0), [14] / [15] the
+ * same of the stack-3 and complex lean passes, [16]-[18] the late double-double lists (real,
+ * complex, real stack 3..8), [19] force-free candidates of one coordinate alone, evaluated at
+ * 64 grid points by the one-coordinate pass (env PDEVAL_ONECOORD=0: none, pass 1 takes them). */
 int pdeval_pass_counts(pdeval_ctx* ctx, int64_t* counts, int max_counts);
 
 /* Diagnostics (force-free): one program at n_pts points (host arrays), tier-1 (tier2 = 0) or

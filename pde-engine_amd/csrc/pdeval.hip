@@ -52,7 +52,8 @@ enum {
     L_DDL = 16,       // the late double-double lists (provisional point passes, after the
     L_DDLC = 17,      // grid): real, complex, real stack 3..8; L_DD / L_DDC / L_DD8 are the
     L_DDL8 = 18,      // early ones (P0_DD, beside the grid passes on the side stream)
-    PD_N_LISTS = 19
+    L_ONE = 19,       // decode pass -> the one-coordinate pass (force-free, pdeval_grid.h PD_ONECOORD)
+    PD_N_LISTS = 20
 };
 // after the list counters in d_counts: the device error word (KernelArgs::errw), then the work
 // queue heads of the persistent list kernels (KernelArgs::qhead), one per launch, zeroed with
@@ -180,6 +181,7 @@ struct pdeval_ctx {
     int deep_parts = PD_DEEP_PARTS;     // the stack-8 lists' waves per candidate (env PDEVAL_DEEP_PARTS)
     bool sort = true;               // env PDEVAL_SORT=0 turns the shape sort off (measurements)
     bool lean_cplx = true;          // env PDEVAL_LEAN_CPLX=0: the generic complex pass (A/B)
+    bool onecoord = true;           // env PDEVAL_ONECOORD=0: one-coordinate candidates stay in pass 1 (A/B)
     // host-path staging: a batch's programs, offsets and output block (outbuf_layout)
     DevBuf<int32_t> d_ops;
     DevBuf<int64_t> d_off;
@@ -235,7 +237,7 @@ Rccl& rccl() {
 
 // in launch order (pass k lasts from event k to event k + 1)
 static const char* const kPassNames[PDEVAL_N_PASSES] = {
-    "pass0_point", "point_deep_complex", "pass1_stack2", "pass2_stack3", "pass3_stack8",
+    "pass0_point", "point_deep_complex", "pass1_stack2", "pass1_onecoord", "pass2_stack3", "pass3_stack8",
     "complex_stack2", "complex_stack8", "tier2_stack2", "tier2_stack3", "tier2_stack8",
     "tier2_complex", "point_dd"};
 
@@ -473,6 +475,7 @@ extern "C" int pdeval_create(int device_id, int problem_id, const double* grid, 
     if ((e = hipSetDevice(device_id)) != hipSuccess) return fail("hipSetDevice", e);
     if (const char* v = getenv("PDEVAL_SORT")) c->sort = atoi(v) != 0;
     if (const char* v = getenv("PDEVAL_LEAN_CPLX")) c->lean_cplx = atoi(v) != 0;
+    if (const char* v = getenv("PDEVAL_ONECOORD")) c->onecoord = atoi(v) != 0;
     if (const char* v = getenv("PDEVAL_GRAPH")) c->use_graph = atoi(v) != 0;
     if (const char* v = getenv("PDEVAL_DD_EARLY")) c->dd_early = atoi(v) != 0;
     if (const char* v = getenv("PDEVAL_DD_SPEC")) c->dd_spec = atoi(v) != 0;
@@ -928,6 +931,12 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     a.hseg = a.hoist && c->hoist_sub ? c->scr.hseg : nullptr;
     a.fmask = c->scr.fmask;
     a.fsum = c->scr.fsum;
+    // the one-coordinate pass (pdeval_grid.h PD_ONECOORD): force-free with Omega = 0 on a grid of
+    // one 64-lane chunk per row, in the full-batch launch (one wave per candidate)
+    const bool one_on = FF && c->onecoord && grid_one_built() && prm.omega2 == 0.0 && c->nx <= 64 && c->ny == 64 &&
+                        grid_parts(n) == 1 && a.ptab;
+    a.one_list = one_on ? c->scr.list[L_ONE] : nullptr;
+    a.one_count = one_on ? cnt + L_ONE : nullptr;
     // ---- the point stage (pdeval_point.h), decided for every candidate before the grid
     // pass 0: real programs of stack <= 2, one candidate per lane; deeper ones -> L_PDEEP,
     // complex-valued ones -> L_CPLX.  Lanes take the candidates sorted by opcode sequence
@@ -1001,9 +1010,17 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     hipLaunchKernelGGL((validate_kernel<PROB, double, 2, true>), dim3((unsigned)std::min<int64_t>(blocks, 256)),
                        dim3(64), (stack_lds<double, K, 2>(1)), s, follow(L_SLOW, L_DEFER, L_ESC));
     HIPCHK(c, hipGetLastError());
+    // the one-coordinate pass: the decoder's list L_ONE, 64 points per candidate
+    mark(3);
+    if (one_on) {
+        hipLaunchKernelGGL(sanitize_list_kernel, dim3(64), dim3(256), 0, s, c->scr.list[L_ONE], cnt + L_ONE, c->scr.cap, n,
+                           a.errw, (uint32_t)ERRW_ONE);
+        launch_grid_one(pgrid, s, follow(L_ONE, -1, L_ESC));
+        HIPCHK(c, hipGetLastError());
+    }
     // pass 2: stack 3, the lean interpreter over the L_DEFER list (64-thread blocks, 2 LDS
     // slots); what it does not take, the generic stack-3 kernel
-    mark(3);
+    mark(4);
     if (dmax > 2) {
         hipLaunchKernelGGL(sanitize_list_kernel, dim3(64), dim3(256), 0, s, c->scr.list[L_DEFER], cnt + L_DEFER, c->scr.cap, n,
                            a.errw, (uint32_t)ERRW_GRID_LIST);
@@ -1015,7 +1032,7 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
         HIPCHK(c, hipGetLastError());
     }
     // pass 3: stack 4..8 (rare; the flattener guarantees <= PDEVAL_MAX_STACK)
-    mark(4);
+    mark(5);
     if (dmax > 3) {
         // (the stack-8 list: a few dozen to a few hundred candidates, each grid split over
         // PD_DEEP_PARTS waves -- pdeval_kernels.h validate_kernel; env PDEVAL_DEEP_PARTS=1: one wave)
@@ -1032,7 +1049,7 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
     if constexpr (FF) {
         // complex passes: candidates not real at the reference point, in complex arithmetic
         // (SymPy evaluates the point exactly, in the complex field: validator.py:363-402)
-        mark(5);
+        mark(6);
         // the lean interpreter in complex arithmetic over the decoded programs; what it does not
         // take (point stage undecided, malformed) the generic complex kernel drains
         if (c->lean_cplx) {
@@ -1048,7 +1065,7 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
                                (stack_lds<cplx, K, 2>(1)), s, follow(L_CPLX, L_CPLX_DEEP, L_ESC_C));
         }
         HIPCHK(c, hipGetLastError());
-        mark(6);
+        mark(7);
         if (dmax > 2) {
             if (c->deep_parts > 1)
                 hipLaunchKernelGGL((validate_kernel<PROB, cplx, PDEVAL_MAX_STACK, true, PD_DEEP_PARTS>),
@@ -1061,30 +1078,30 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
             HIPCHK(c, hipGetLastError());
         }
     } else {
-        mark(5);
         mark(6);
+        mark(7);
     }
     // tier 2 (pdeval_tier2.h): re-decide every tier-1 grid failure with error bounds, by stack
     KernelArgs t = queue(follow(L_ESC, L_ESC_DEEP, L_ESC), Q_T2);
-    mark(7);
+    mark(8);
     // (PARTS waves per entry: pdeval_tier2.h)
     hipLaunchKernelGGL((tier2_kernel<PROB, double, 2, false, PD_T2_PARTS>), dim3((unsigned)std::min<int64_t>(n * PD_T2_PARTS, 8192)),
                        dim3(64), (tier2_lds<double, K, 2>()), s, t);
     HIPCHK(c, hipGetLastError());
-    mark(8);
+    mark(9);
     if (dmax > 2) {
         hipLaunchKernelGGL((tier2_kernel<PROB, double, 3, false, PD_T2_PARTS>), dim3((unsigned)std::min<int64_t>(n * PD_T2_PARTS, 4096)),
                            dim3(64), (tier2_lds<double, K, 3>()), s, queue(follow(L_ESC_DEEP, L_ESC_DEEP2, L_ESC), Q_T2_3));
         HIPCHK(c, hipGetLastError());
     }
-    mark(9);
+    mark(10);
     if (dmax > 3) {
         hipLaunchKernelGGL((tier2_kernel<PROB, double, PDEVAL_MAX_STACK>), dim3((unsigned)std::min<int64_t>(n, 512)),
                            dim3(64), (tier2_lds<double, K, PDEVAL_MAX_STACK>()), s, queue(follow(L_ESC_DEEP2, -1, L_ESC), Q_T2_8));
         HIPCHK(c, hipGetLastError());
     }
     if constexpr (FF) {
-        mark(10);
+        mark(11);
         hipLaunchKernelGGL((tier2_kernel<PROB, cplx, 4, false, PD_T2_PARTS_C>),
                            dim3((unsigned)std::min<int64_t>(n * PD_T2_PARTS_C, 4096)), dim3(64),
                            (tier2_lds<cplx, K, 4>()), s, queue(follow(L_ESC_C, L_ESC_C_DEEP, L_ESC_C), Q_T2_C));
@@ -1097,11 +1114,11 @@ static int launch_all(pdeval_ctx* c, const int32_t* d_ops, int64_t n_words, cons
             HIPCHK(c, hipGetLastError());
         }
     } else {
-        mark(10);
+        mark(11);
     }
     // ---- the point stage's double-double tier (pdeval_point.h): candidates fp64 left
     // undecided, and provisional point passes whose grid stage rejected
-    mark(11);
+    mark(12);
     if (early) {
         // join the side stream; the late lists (provisional point passes the grid classes
         // now make relevant), then the early tier's classes applied to the final grid classes

@@ -66,7 +66,8 @@ constexpr uint64_t kVarMask = op_bit(PDOP_MUL_X) | op_bit(PDOP_MUL_Y) | op_bit(P
 // every grid row of a candidate.  decode_kernel does it once per candidate, before pass 1, into
 // a word array laid out like the programs (same offsets, n_words long):
 //   at the header position     0 and the program's true stack depth in bits 8-15, or 0xff if
-//                              the lean passes cannot take it (lean_prescan<3> fails)
+//                              the lean passes cannot take it (lean_prescan<3> fails), or 1 / 2
+//                              in the low byte for grid_one_kernel's candidates (PD_ONECOORD)
 //   at each opcode position    op (bits 0-7), the word's own bits 8-16 (POWN / coordinate power
 //                              n, axis), the dispatch group (17-19), last-opcode bit (20), the
 //                              distance to the next opcode (21-25: 1, 3 or 5, more after folded
@@ -151,6 +152,18 @@ __device__ __forceinline__ bool neg_fold_ok(const int32_t* prog, int plen) {
 #define PD_HOIST_SUB 1
 #endif
 template <int PROB> constexpr bool hoist_sub() { return PD_HOIST_SUB && PROB != PDEVAL_PROBLEM_FORCE_FREE; }
+// ---- candidates of one coordinate alone (PD_ONECOORD, force-free with Omega = 0).  u = f(rho):
+// the 64 lanes of a grid row compute one jet and one epilogue 64 times; u = f(z): the 64 rows
+// repeat each other (the program reads no x, and the epilogue's powers of 1/rho multiply only
+// coefficients c[i >= 1][j], exact zeros of such a jet -- FFEpi::eval_p).  Of the 4,096 grid
+// points 64 are distinct.  The decoder marks these candidates in the low byte of the decoded
+// header word (1: of x alone, 2: of y alone; pass 1 returns at once for them) and appends them to
+// a.one_list; grid_one_kernel (below) evaluates the 64 points and writes what the 64 x 64 would.
+#ifndef PD_ONECOORD
+#define PD_ONECOORD 1
+#endif
+constexpr uint32_t DEC_ONE_X = 1u, DEC_ONE_Y = 2u;
+__device__ __forceinline__ bool dec_one(uint32_t dh) { return ((dh & 0xffu) - 1u) < 2u; }
 constexpr uint64_t kHeavyMask = op_bit(PDOP_MUL) | op_bit(PDOP_DIV) | op_bit(PDOP_RDIV) | op_bit(PDOP_RDIVC) |
                                 op_bit(PDOP_POWN) | op_bit(PDOP_POW) | op_bit(PDOP_SQRT) | op_bit(PDOP_EXP) |
                                 op_bit(PDOP_LOG) | op_bit(PDOP_MUL_P) | op_bit(PDOP_DIV_P) | op_bit(PDOP_RDIV_P) |
@@ -362,7 +375,20 @@ __global__ __launch_bounds__(256) void decode_kernel(KernelArgs a) {
         const uint32_t at = (uint32_t)hoist_last + (((uint32_t)dec[hoist_last] >> DEC_DIST) & DEC_DIST_MAX);
         if (at < (uint32_t)plen && at < (1u << 14)) hp = at;   // (not a whole program of x alone)
     }
-    dec[0] = ok ? (int32_t)(((uint32_t)dmax << 8) | (sg[1] < 0 ? 1u << 16 : 0u) | (hp << 17) |
+    // PD_ONECOORD: a real program of stack <= 2 whose value depends on exactly one coordinate and
+    // whose grid the point stage left to run (a.one_list is set by the host only for force-free
+    // with Omega = 0, nx <= 64, ny == 64 and one wave per candidate)
+    uint32_t one = 0u;
+    // (the header's own depth too: pass 1 defers by it before it reads the decoded word)
+    if (PD_ONECOORD && PROB == PDEVAL_PROBLEM_FORCE_FREE && a.one_list && a.pstate && ok && dmax <= 2 &&
+        ((hdr >> 8) & 0xffu) <= 2u && (msk[1] == 1u || msk[1] == 2u) && !(hdr & (PDEVAL_FLAG_COMPLEX | PDEVAL_FLAG_NOCOORD))) {
+        const uint8_t ps = a.pstate[cand];
+        // (marked only once it is on the list: a full list leaves the candidate to pass 1)
+        if (!(ps & P0_CPLX) && (ps & 3) != P0_NONE && ((ps & 3) != P0_REJECT || a.prm.full_grid) &&
+            list_append(a.one_list, a.one_count, a.list_capacity, cand))
+            one = msk[1] == 1u ? DEC_ONE_X : DEC_ONE_Y;
+    }
+    dec[0] = ok ? (int32_t)(one | ((uint32_t)dmax << 8) | (sg[1] < 0 ? 1u << 16 : 0u) | (hp << 17) |
                             (hp && hoist_y ? 1u << 31 : 0u)) : (int32_t)0xff;
     // the hoisted segment: the heaviest one after the prefix (force-free: x alone), its first
     // opcode word replaced by DOP_PUSH_H, the original kept in a.hseg with its span and kind
@@ -1108,6 +1134,10 @@ __device__ __forceinline__ void grid_body(const KernelArgs& a, int64_t cand, int
     uint32_t h_w0 = 0u;
     if (!slow) {
         const uint32_t dh = rd_word(a.dec + beg);
+        // on the decoder's one-coordinate list: grid_one_kernel evaluates it (PD_ONECOORD)
+        if constexpr (PD_ONECOORD && PROB == PDEVAL_PROBLEM_FORCE_FREE && MAXD == 2 && !CX) {
+            if (dec_one(dh)) return;
+        }
         slow = (dh & 0xffu) != 0u || (int)((dh >> 8) & 0xffu) > MAXD;
         u_sgn = (dh & 0x10000u) << 15;
         if (!CX && hoist_sub<PROB>() && a.hseg && !slow) {
@@ -1435,5 +1465,99 @@ __global__ __launch_bounds__(64, PD_CPLX_WAVES_PER_SIMD) void grid_cplx_kernel(K
                                                       (int)(wp % parts), parts);
     }
 }
+
+// The one-coordinate pass (PD_ONECOORD): the decoder's list a.list = L_ONE, persistent one-wave
+// blocks, one run of the program and one epilogue per candidate.  Of x alone: lane r is grid row
+// r (the per-lane-x copy of the interpreter, as the hoisted prefix runs it), and what the row's
+// 64 lanes would all compute is this lane's result.  Of y alone: lane l is the ordinate gy[l],
+// at row 0's x (no opcode reads x, and the epilogue's powers of 1/rho multiply only the
+// coefficients c[i >= 1][j], which are 0 -- or NaN at every row alike), and every row repeats it.
+// The counts, the maximum of q over the same set of values, the failing-lane words of tier 2 and
+// the fingerprint points are then those of grid_body's 64 rows.  (a.ny == 64, a.nx <= 64, Omega
+// = 0 and the full-batch launch: the host sets a.one_list only then.)
+#ifndef PD_ONE_WAVES_PER_SIMD
+#define PD_ONE_WAVES_PER_SIMD 4
+#endif
+#if PD_ONECOORD
+static_assert(PD_DIVFREE && PD_EPI_TABLE_RCP, "grid_one_kernel restates grid_body's default epilogue");
+__device__ __forceinline__ void grid_one_body(const KernelArgs& a, int64_t cand, int lane, double* stk) {
+    constexpr int K = 4;
+    using L = Lean<double, K, 1, 2>;
+    const int64_t beg = a.offsets[cand], end = a.offsets[cand + 1];
+    if (!(beg >= 0 && end > beg && end <= a.n_words)) return;   // (never on the list: the decoder checked)
+    const uint32_t hdr = rd_word(a.ops + beg);
+    const uint32_t dh = rd_word(a.dec + beg);
+    if (!dec_one(dh)) return;   // (not marked: pass 1 took it)
+    const bool xa = (dh & 0xffu) == DEC_ONE_X;
+    const uint32_t u_sgn = (dh & 0x10000u) << 15;
+    const uint8_t ps = (uint8_t)__builtin_amdgcn_readfirstlane((int)a.pstate[cand]);
+    const int r = xa ? min(lane, a.nx - 1) : 0;
+    const double y0 = a.gy[lane];
+    const double inv_y0 = rcp(y0);
+    const double x[1] = {a.gx[r]}, inv_x[1] = {a.gx[a.nx + r]};   // 1/x: the host table, = rcp(x)
+    PowTab<1> pt;
+    pt.sx = a.nx * (K + 1);
+    pt.sy = (K + 1) * a.ny;
+    pt.ny = a.ny;
+    pt.px[0] = a.ptab + (size_t)r * (K + 1);
+    pt.py = a.ptab + (size_t)PTAB_N * a.nx * (K + 1) + lane;
+    typename L::J u[1];
+    L::template run<true>(a.dec + beg, x, y0, inv_x, inv_y0, u, stk, lane, pt);
+    const double inv_x2 = inv_x[0] * inv_x[0], inv_x3 = inv_x2 * inv_x[0];   // as grid_body forms them
+    const PointResult p = ff_epilogue_p<double>(u[0].c, inv_x[0], inv_x2, inv_x3, x[0], 0.0);
+    // the distinct points: rows < nx (x alone; lanes past nx repeat the last row), 64 ordinates
+    const uint64_t live = xa && a.nx < 64 ? (1ull << a.nx) - 1ull : ~0ull;
+    const bool mine = (live >> lane) & 1ull;
+    const int rep = xa ? a.ny : a.nx;   // grid points per distinct point
+    GridMax<false> gm;
+    gm.add(p.finite & mine, p.res_abs, p.scale);
+    const bool grad_nz = ((ps & P0_GRAD) != 0) | (mine & p.finite & !p.grad_zero);
+    const uint64_t fin = p.fin_lanes & live;
+    const uint64_t fm = fin & lane_mask(grid_fails(p.res_abs, p.scale, a.prm.tau_grid));
+    const int nfin = rep * (int)__popcll(fin), nbad = rep * (int)__popcll(fm);
+    // tier 2's failing-lane words, one per row: all 64 lanes of a failing row (x alone), the
+    // failing ordinates in every row (y alone); sparse as grid_body stores them
+    if (a.fmask && (ps & 3) != P0_REJECT) {
+        const bool fsparse = PD_FMASK_SPARSE && a.fsum;
+        const uint64_t word = xa ? (((fm >> lane) & 1ull) ? ~0ull : 0ull) : fm;
+        if (lane < a.nx && (!fsparse || word)) a.fmask[cand * (int64_t)a.nx + lane] = word;
+        if (a.fsum && lane == 0)
+            a.fsum[cand] = !fsparse ? ~0ull : xa ? fm : fm ? (a.nx < 64 ? (1ull << a.nx) - 1ull : ~0ull) : 0ull;
+    }
+    if (a.out.fingerprint) {
+#pragma unroll
+        for (int f = 0; f < PDEVAL_FP_N; ++f) {
+            const int rel = a.fp_pts[f] - a.n_ref;   // uniform
+            if (rel >= 0 && rel < a.nx * a.ny && lane == (xa ? rel / a.ny : rel % a.ny)) {
+                const double v = fp_value(u[0].c[0]);
+                a.out.fingerprint[cand * PDEVAL_FP_N + f] =
+                    __hiloint2double((int)((uint32_t)__double2hiint(v) ^ u_sgn), __double2loint(v));
+            }
+        }
+    }
+    const double qmax = wave_max(gm.q());
+    const bool any_grad = __any(grad_nz) && !(ps & P0_CONST);
+    if (lane == 0)
+        grid_finish(a, cand, hdr, PDEVAL_PROBLEM_FORCE_FREE, (ps & 3) == P0_REJECT, qmax, nbad, nfin,
+                    a.nx * a.ny - nfin, any_grad, (ps & P0_CONST) != 0);
+}
+
+__global__ __launch_bounds__(64, PD_ONE_WAVES_PER_SIMD) void grid_one_kernel(KernelArgs a) {
+#ifndef PD_HOST_SIM
+    extern __shared__ __align__(16) unsigned char pd_lds[];
+#else
+    static unsigned char pd_lds[1];
+#endif
+    double* stk = reinterpret_cast<double*>(pd_lds);
+    int64_t nwork = (int64_t)(*a.list_count);
+    if (nwork > a.list_capacity) nwork = a.list_capacity;
+    WorkQueue q;
+    for (int64_t wi = q.first(a); wi < nwork; wi = q.next(a, wi)) {
+        // (entries checked before the launch: sanitize_list_kernel)
+        const int64_t cand = (int64_t)__builtin_amdgcn_readfirstlane((int)a.list[wi]);
+        grid_one_body(a, cand, threadIdx.x & 63, stk);
+    }
+}
+#endif
 
 }  // namespace pd

@@ -71,6 +71,16 @@ void launch_grid_cplx(unsigned blocks, hipStream_t s, const KernelArgs& a, int64
         hipLaunchKernelGGL(grid_cplx_kernel<false>, dim3(blocks), dim3(64), l, s, a, slow_list, slow_count, 1);
 }
 
+bool grid_one_built() { return PD_ONECOORD != 0; }
+
+void launch_grid_one(unsigned blocks, hipStream_t s, const KernelArgs& a) {
+#if PD_ONECOORD
+    hipLaunchKernelGGL(grid_one_kernel, dim3(blocks), dim3(64), (grid_lds<PDEVAL_PROBLEM_FORCE_FREE, 2>(1)), s, a);
+#else
+    (void)blocks, (void)s, (void)a;
+#endif
+}
+
 void launch_grid_list(int problem, unsigned blocks, hipStream_t s, const KernelArgs& a,
                       int64_t* slow_list, int32_t* slow_count, int parts) {
     const size_t lff = grid_lds<PDEVAL_PROBLEM_FORCE_FREE, 3>(1), lk = grid_lds<PDEVAL_PROBLEM_KERR, 3>(1);

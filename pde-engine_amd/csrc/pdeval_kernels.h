@@ -100,6 +100,9 @@ struct KernelArgs {
     uint32_t* hoist_own;        // one owner word per slot (0 = free): a running wave holds the
                                 // slot of its candidate (pdeval_grid.h hoist_acquire)
     int hoist_pool;             // slots per XCD (8 pools); a split launch indexes by candidate
+    int64_t* one_list;          // decoder: the force-free candidates of one coordinate alone, which
+    int32_t* one_count;         // grid_one_kernel evaluates at 64 points (pdeval_grid.h PD_ONECOORD);
+                                // NULL = none (every candidate takes pass 1)
     // the problem's constants per stage (PDEVAL_IMM_PRM; Kerr M, a): point stage (fp64 and
     // double-double) and the constant test / grid stage
     PrmTab<double> prm_pt, prm_grid;
@@ -144,7 +147,7 @@ struct WorkQueue {
 // error word (bit `code`) and the caller skips it, instead of indexing the batch with it.
 enum : uint32_t {
     ERRW_PERM = 1u, ERRW_GRID_LIST = 2u, ERRW_GENERIC = 4u, ERRW_POINT_LIST = 8u, ERRW_DD = 16u,
-    ERRW_DD_APPLY = 32u, ERRW_TIER2 = 64u, ERRW_CPLX = 128u, ERRW_HOIST = 256u
+    ERRW_DD_APPLY = 32u, ERRW_TIER2 = 64u, ERRW_CPLX = 128u, ERRW_HOIST = 256u, ERRW_ONE = 512u
 };
 #ifndef PD_CHECK_LISTS
 #define PD_CHECK_LISTS 1

@@ -34,6 +34,10 @@ void launch_grid(int problem, int64_t n, hipStream_t s, const KernelArgs& a,
 // the complex pass (force-free): persistent over the list a.list (L_CPLX), complex jets
 void launch_grid_cplx(unsigned blocks, hipStream_t s, const KernelArgs& a, int64_t* slow_list, int32_t* slow_count,
                       int parts);
+// the one-coordinate pass (force-free, pdeval_grid.h PD_ONECOORD): persistent over the decoder's
+// list a.list (L_ONE); grid_one_built(): whether the grid unit was built with it
+bool grid_one_built();
+void launch_grid_one(unsigned blocks, hipStream_t s, const KernelArgs& a);
 void launch_grid_list(int problem, unsigned blocks, hipStream_t s, const KernelArgs& a,
                       int64_t* slow_list, int32_t* slow_count, int parts);
 // sort the batch by opcode sequence (pdeval_sort.hip): keys/idx hold 2 x n each, the

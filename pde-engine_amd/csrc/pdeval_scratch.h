@@ -8,7 +8,7 @@
 
 namespace pd {
 
-constexpr int kScratchLists = 19;          // PD_N_LISTS of pdeval.hip
+constexpr int kScratchLists = 20;         // PD_N_LISTS of pdeval.hip
 constexpr int64_t kScratchMinCap = 1024;   // candidates the scratch holds at least
 constexpr int64_t kScratchMinDec = 4096;   // decoded words it holds at least
 

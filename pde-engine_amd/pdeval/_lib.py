@@ -41,8 +41,9 @@ UNIQUE_ID_BYTES = 128
 LIST_NAMES = ('defer_stack3', 'complex', 'defer_stack8', 'tier2', 'tier2_stack3', 'tier2_complex',
               'complex_stack8', 'tier2_stack8', 'point_deep', 'point_dd', 'point_dd_complex',
               'point_dd_stack8', 'tier2_complex_stack8', 'grid_slow', 'grid_slow_stack3',
-              'grid_slow_complex')
-N_PASSES = 12
+              'grid_slow_complex', 'point_dd_late', 'point_dd_late_complex', 'point_dd_late_stack8',
+              'one_coord')
+N_PASSES = 13
 FOL_MAX_PROBES = 32          # PDEVAL_FOL_MAX_PROBES
 FOL_AXIS = 1                 # PDEVAL_FOL_AXIS: functions of one coordinate form one class per axis
 FOL_LINK = 2                 # PDEVAL_FOL_LINK: a registry records the links between its classes
