@@ -329,7 +329,25 @@ int pdeval_comm_destroy(pdeval_ctx* ctx);
  * a == 0, c == 0, b != 0, d != 0 (both along z: the planes z = const).  The test is on the
  * operands, not the products; such a point adds 1 to n_used and 0 to qmax.  A zero gradient
  * still matches nothing.  Every entry point below takes the flag from the parameters it is given
- * (a registry: from those it was created with); with the bit clear every result is what it was. */
+ * (a registry: from those it was created with); with the bit clear every result is what it was.
+ * Complex-valued rows (flags & PDEVAL_FOL_CPLX; off by default): a program with
+ * PDEVAL_FLAG_COMPLEX, or one that is not real on the sample grid (the square root of a negative
+ * value everywhere), has an all-NaN field and stays unclassified, although the validator decides
+ * it in the complex field and may accept it.  A complex u is still a real foliation where its
+ * gradient is a complex multiple of a real vector: sqrt(-(rho**2 + z**2)) = i r has the circles of
+ * rho**2 + z**2 as level sets.  With the flag, after the real field kernel, a row whose header has
+ * PDEVAL_FLAG_COMPLEX or whose real pass left n_finite < min_points (and whose list entry,
+ * offsets, header and stack depth pass the same checks) is run in order-1 complex jets, the
+ * arithmetic of the validator's complex passes, and reduced point by point to a real gradient of
+ * the same direction.  With u, a = u_rho, b = u_z complex: a part that is not finite gives (NaN,
+ * NaN); a = b = 0 gives (0, 0); otherwise the pivot w is a if |a| >= |b|, else b, o the other one,
+ * t = o conj(w), and the point is (NaN, NaN) unless |Im t| <= tau |w| |o| (the two components have
+ * the same phase up to sign: a real direction); then the pivot's component is |w| and the other
+ * one Re t / |w|.  The pivot's component is positive: the Jacobian test does not depend on the
+ * real factor per point, the equal-field comparison of a tag does.  An exact zero component stays
+ * an exact zero.  Every other row keeps the bits the real kernel wrote, n_finite is rewritten for
+ * the rows taken, and nothing after the fields changes.  With the bit clear nothing new is
+ * launched and every result is what it was.                                                     */
 typedef struct pdeval_fol_params {
     double tau;          /* a usable point is bad iff |J| > tau * S (1e-7, the grid's tau_grid) */
     int32_t m;           /* sample grid m x m, 4 <= m <= 64 (16)                                 */
@@ -339,6 +357,8 @@ typedef struct pdeval_fol_params {
 #define PDEVAL_FOL_AXIS 1   /* functions of one coordinate form one class per axis (above)       */
 #define PDEVAL_FOL_LINK 2   /* a registry also records the links between its classes (below);
                                pdeval_jacobian_match and pdeval_foliation_classes ignore it      */
+#define PDEVAL_FOL_CPLX 4   /* rows that are not real-valued take the complex field pass (above);
+                               a flag of the calls that compute fields from programs             */
 #define PDEVAL_FOL_MAX_PROBES 32
 int pdeval_default_fol_params(pdeval_fol_params* out);
 /* Device pointers, asynchronous on `stream` (NULL = the context's).  d_mask[row]: bit k set iff
@@ -356,8 +376,9 @@ int pdeval_jacobian_match(pdeval_ctx* ctx, const double* d_rows_field, int64_t n
  * whole row is NaN for a program with PDEVAL_FLAG_COMPLEX, one the interpreter declines
  * (malformed, unsupported opcode, stack deeper than PDEVAL_MAX_STACK), one whose offsets fall
  * outside [0, n_words] or a list entry outside [0, n); such programs are never dereferenced.
- * d_n_finite (may be NULL): per row, the points with a finite u_rho.  Asynchronous on `stream`
- * (NULL = the context's).                                                                      */
+ * d_n_finite (may be NULL): per row, the points with a finite u_rho.  With PDEVAL_FOL_CPLX the
+ * rows described above are recomputed by the complex pass and d_n_finite is required (it
+ * selects them): NULL is PDEVAL_ERR_ARG.  Asynchronous on `stream` (NULL = the context's).     */
 int pdeval_gradient_fields(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
                            int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
                            double* d_field, int32_t* d_n_finite, void* stream);

@@ -99,7 +99,7 @@ using FolInterp = Interp<double, 1, kFolMaxD>;
 // program word is read -- when the list entry lies outside [0, n) or the candidate's
 // [offsets[c], offsets[c + 1]) does not lie inside [0, n_words]; otherwise the header word is
 // read, and ok = false for a complex program, a non-header first word or a stack deeper than
-// kFolMaxD.
+// kFolMaxD.  (fol_program_cplx below restates the range checks: keep the two in step.)
 struct FolProg {
     const int32_t* words;
     int len;
@@ -142,6 +142,78 @@ __device__ __forceinline__ FolField fol_field_point(const FolProg& pr, const Fol
     f.b = ok ? u.c[ji(0, 1)] : nan;
     f.fin = ok;
     return f;
+}
+
+// ---------------------------------------------------------------- complex-valued rows (host + device)
+// PDEVAL_FOL_CPLX (DESIGN.md §14 "Complex-valued rows"): a row that is not real-valued on the
+// grid is run in order-1 complex jets and reduced, point by point, to a real gradient of the same
+// direction.  A complex u is a real foliation where its gradient is a complex multiple of a real
+// vector, (a, b) = lambda (n_rho, n_z): then a and b have the same phase up to sign, i.e.
+// Im(o conj(w)) = 0 for the two components w, o.
+// The rule, on u, a = u_rho, b = u_z:
+//   1. any of the six real parts not finite: (NaN, NaN), not counted in n_finite;
+//   2. ha = |a|, hb = |b| (hypot); both 0: (0, 0) -- finite, matches nothing, as a real zero gradient;
+//   3. the pivot w is a if ha >= hb, else b; o the other one, h = |w|, ho = |o|;
+//      t = o conj(w): tr = Re o Re w + Im o Im w, ti = Im o Re w - Re o Im w, each of the four
+//      products rounded separately (no FMA: the host restatement computes the same doubles);
+//   4. the direction is real iff |ti| <= tau (h ho) -- |sin| of the phase difference against the
+//      parameters' own tau; if not, (NaN, NaN): no real foliation at this point;
+//   5. the pivot's component is h, the other one tr / h; either not finite: (NaN, NaN).
+// Sign convention: the pivot's component is positive.  The Jacobian test does not see it (J scales
+// by the real factor per point, S by its modulus), but the equal-field tag rule does: a real u
+// that took this path (n_finite < min_points) has the field (|a|, b sgn a) where a is the pivot.
+// An exact zero component stays an exact zero (o = 0 gives tr / h = 0), so the axis rule and
+// fol_kind_kernel see i f(rho) as a function of rho alone without a tolerance.
+struct FolCplxPoint {
+    double a, b;
+    bool fin;
+};
+PD_HD FolCplxPoint fol_cplx_point(cplx u, cplx a, cplx b, double tau) {
+#pragma clang fp contract(off)
+    const double nan = __builtin_nan("");
+    const FolCplxPoint none{nan, nan, false};
+    if (!(finite_(u) && finite_(a) && finite_(b))) return none;
+    const double ha = hypot(a.re, a.im), hb = hypot(b.re, b.im);
+    if (ha == 0.0 && hb == 0.0) return {0.0, 0.0, true};
+    const bool pa = ha >= hb;
+    const cplx w = pa ? a : b, o = pa ? b : a;
+    const double h = pa ? ha : hb, ho = pa ? hb : ha;
+    const double rr = o.re * w.re, ii = o.im * w.im, ir = o.im * w.re, ri = o.re * w.im;
+    const double tr = rr + ii, ti = ir - ri;
+    if (!(fabs(ti) <= tau * (h * ho))) return none;
+    const double q = tr / h;
+    if (!(finite_(h) && finite_(q))) return none;
+    return {pa ? h : q, pa ? q : h, true};
+}
+
+// The complex stack of one wave: (MAXD - 1) x 3 x 64 cplx = 21,504 bytes.  One wave per block:
+// seven blocks fit a CU's 160 KiB of LDS (two-wave blocks would fit three: six waves; four-wave
+// blocks one), and a row that is not taken gives its slot back at once.
+constexpr int kFolCplxStack = (kFolMaxD - 1) * nc(1) * 64;   // cplx per wave
+using FolCplxInterp = Interp<cplx, 1, kFolMaxD>;
+
+// fol_program for the complex pass: the same range checks (no program word is read for an entry
+// that fails them), then the header word; ok also for a program with PDEVAL_FLAG_COMPLEX, which
+// `flagged` reports.  The checks are fol_program's, line for line, so that the real kernel stays
+// as it is: a change to either function's checks belongs in both.
+struct FolCplxProg {
+    const int32_t* words;
+    int len;
+    bool ok, flagged;
+};
+__device__ __forceinline__ FolCplxProg fol_program_cplx(const int32_t* ops, int64_t n_words, const int64_t* offsets,
+                                                        int64_t n, const int64_t* list, int64_t row) {
+    FolCplxProg r{ops, 0, false, false};
+    const int64_t cand = list ? list[row] : row;
+    if (cand < 0 || cand >= n) return r;
+    const int64_t beg = offsets[cand], end = offsets[cand + 1];
+    if (!(beg >= 0 && end > beg && end <= n_words && end - beg < (1 << 24))) return r;
+    r.words = ops + beg;
+    r.len = (int)(end - beg);
+    const uint32_t hdr = rd_word(r.words);
+    r.ok = (hdr & 0xffu) == 0u && (int)((hdr >> 8) & 0xffu) <= kFolMaxD;
+    r.flagged = (hdr & PDEVAL_FLAG_COMPLEX) != 0u;
+    return r;
 }
 
 // ---------------------------------------------------------------- the leader rule (host)
@@ -264,6 +336,13 @@ struct FolFieldArgs {
     int32_t* n_finite;         // optional, n_list, zeroed by the caller
 };
 void launch_fol_field(const FolFieldArgs& a, hipStream_t s);
+// fol_field_cplx_kernel (PDEVAL_FOL_CPLX), after fol_field_kernel on the same stream: n_finite is
+// required, it selects the rows
+struct FolFieldCplxArgs : FolFieldArgs {
+    double tau;
+    int min_points;
+};
+void launch_fol_field_cplx(const FolFieldCplxArgs& a, hipStream_t s);
 
 // The pair scan of a registry (pdeval_fol_registry.hip, fol_scan): rows of fields against the
 // resident leaders.  What both of its modes take.

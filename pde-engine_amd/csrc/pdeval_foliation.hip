@@ -138,6 +138,57 @@ void launch_fol_field(const FolFieldArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(fol_field_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, a);
 }
 
+// The complex pass (PDEVAL_FOL_CPLX), launched after fol_field_kernel on the same stream.  One
+// wave per list row, one wave per block; lanes are sample points and the wave loops over the
+// row's chunks.  (One wave per (row, chunk), as above, does not fit: the selection reads
+// n_finite[row], which the chunks of a row would be updating under each other.)  The wave reads
+// the count once, before it writes anything, and leaves wave-uniformly unless the row is taken:
+// entry and offsets in range, a header first, stack <= kFolMaxD, and either PDEVAL_FLAG_COMPLEX
+// in the header or n_finite[row] < min_points after the real pass.  A row that is not taken
+// keeps the bits the real kernel wrote.  A taken row is run in order-1 complex jets -- the
+// arithmetic of the validator's complex passes, so the branches of sqrt, pow and log are those
+// the verdict was reached with -- with the operand stack in LDS, [slot][coef][lane] (each lane
+// touches only its own words: no barrier), and fol_cplx_point reduces each point to a real
+// gradient.  A run that does not return RUN_OK (wave-uniform) leaves the row NaN throughout.
+// Lanes past m^2 compute the last point again and store nothing; lane 0 stores the row's new
+// count with a plain store.
+__global__ __launch_bounds__(64) void fol_field_cplx_kernel(FolFieldCplxArgs a) {
+    __shared__ cplx fol_clds[kFolCplxStack];
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    if (row >= a.n_list) return;
+    const int nf0 = a.n_finite[row];
+    const FolCplxProg pr = fol_program_cplx(a.ops, a.n_words, a.offsets, a.n, a.list, row);
+    if (!(pr.ok && (pr.flagged || nf0 < a.min_points))) return;
+    const int mm = a.grid.m * a.grid.m;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double* out = a.field + row * 2 * (int64_t)mm;
+    int nf = 0;
+    bool run_ok = true;
+    for (int c = 0; c < a.n_chunk; ++c) {
+        const int p = c * kFolChunk + lane;
+        const bool active = p < mm;
+        FolCplxPoint f{nan, nan, false};
+        if (run_ok) {
+            double x, y;
+            fol_point_xy(a.grid, active ? p : mm - 1, x, y);
+            FolCplxInterp::J u;
+            run_ok = FolCplxInterp::run(pr.words, 1, pr.len, x, y, u, fol_clds, lane, a.prm) == RUN_OK;
+            if (run_ok) f = fol_cplx_point(u.c[0], u.c[ji(1, 0)], u.c[ji(0, 1)], a.tau);
+        }
+        if (active) {
+            out[p] = f.a;
+            out[mm + p] = f.b;
+        }
+        nf += count_lanes(active && f.fin);
+    }
+    if (lane == 0) a.n_finite[row] = nf;
+}
+
+void launch_fol_field_cplx(const FolFieldCplxArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(fol_field_cplx_kernel, dim3((unsigned)a.n_list), dim3(64), 0, s, a);
+}
+
 }  // namespace pd
 
 using namespace pd;
@@ -210,10 +261,15 @@ int fol_hip_fail(pdeval_ctx* c, const char* what, hipError_t e) {
     return fol_fail(c, PDEVAL_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
 }
 
-// zeroes d_n_finite (if given) and launches the field kernel on s
+// zeroes d_n_finite (if given) and launches the field kernel on s, then, with PDEVAL_FOL_CPLX, the
+// complex pass (one block per row; it needs d_n_finite)
 int fol_fields_launch(pdeval_ctx* c, const FolCtx& v, const pdeval_fol_params& prm, const int32_t* d_ops,
                       int64_t n_words, const int64_t* d_offsets, int64_t n, const int64_t* d_list, int64_t n_list,
                       double* d_field, int32_t* d_n_finite, hipStream_t s) {
+    // (n_list <= PDEVAL_MAX_BATCH, fol_check: the complex pass's n_list blocks are one launch)
+    if ((prm.flags & PDEVAL_FOL_CPLX) && !d_n_finite)
+        return fol_fail(c, PDEVAL_ERR_ARG,
+                        "pdeval_gradient_fields: PDEVAL_FOL_CPLX needs d_n_finite (the complex pass selects its rows by it)");
     FolFieldArgs a{};
     a.ops = d_ops;
     a.n_words = n_words;
@@ -232,6 +288,14 @@ int fol_fields_launch(pdeval_ctx* c, const FolCtx& v, const pdeval_fol_params& p
         return fol_hip_fail(c, "hipMemsetAsync", e);
     launch_fol_field(a, s);
     if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_field_kernel", e);
+    if (prm.flags & PDEVAL_FOL_CPLX) {
+        FolFieldCplxArgs ca{};
+        static_cast<FolFieldArgs&>(ca) = a;
+        ca.tau = prm.tau;
+        ca.min_points = prm.min_points;
+        launch_fol_field_cplx(ca, s);
+        if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_field_cplx_kernel", e);
+    }
     return PDEVAL_OK;
 }
 

@@ -47,6 +47,7 @@ N_PASSES = 13
 FOL_MAX_PROBES = 32          # PDEVAL_FOL_MAX_PROBES
 FOL_AXIS = 1                 # PDEVAL_FOL_AXIS: functions of one coordinate form one class per axis
 FOL_LINK = 2                 # PDEVAL_FOL_LINK: a registry records the links between its classes
+FOL_CPLX = 4                 # PDEVAL_FOL_CPLX: rows that are not real-valued take the complex field pass
 
 
 class Params(C.Structure):
@@ -77,7 +78,7 @@ class KerrConstants(C.Structure):
 
 class FolParams(C.Structure):
     """pdeval_fol_params (include/pdeval.h): the Jacobian test on an m x m sample grid; ``flags``
-    holds the PDEVAL_FOL_* bits (``FOL_AXIS``, ``FOL_LINK``)."""
+    holds the PDEVAL_FOL_* bits (``FOL_AXIS``, ``FOL_LINK``, ``FOL_CPLX``)."""
     _fields_ = [('tau', C.c_double), ('m', C.c_int32), ('min_points', C.c_int32), ('flags', C.c_int32)]
 
 
@@ -174,15 +175,18 @@ def default_fol_params() -> FolParams:
 
 
 def fol_params(params: Optional[FolParams] = None, axis: Optional[bool] = None,
-               link: Optional[bool] = None) -> FolParams:
+               link: Optional[bool] = None, cplx: Optional[bool] = None) -> FolParams:
     """A copy of ``params`` (None: the defaults); ``axis`` True / False sets / clears ``FOL_AXIS``
-    in its flags and ``link`` ``FOL_LINK`` (a registry's flag), None leaves them."""
+    in its flags, ``link`` ``FOL_LINK`` (a registry's flag) and ``cplx`` ``FOL_CPLX`` (rows that are
+    not real-valued take the complex field pass), None leaves them."""
     src = params if params is not None else default_fol_params()
     p = FolParams(src.tau, src.m, src.min_points, src.flags)
     if axis is not None:
         p.flags = (int(p.flags) | FOL_AXIS) if axis else (int(p.flags) & ~FOL_AXIS)
     if link is not None:
         p.flags = (int(p.flags) | FOL_LINK) if link else (int(p.flags) & ~FOL_LINK)
+    if cplx is not None:
+        p.flags = (int(p.flags) | FOL_CPLX) if cplx else (int(p.flags) & ~FOL_CPLX)
     return p
 
 
@@ -358,7 +362,8 @@ class Context:
     def gradient_fields(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int,
                         d_field: int, d_n_finite: int = 0, params: Optional[FolParams] = None, stream: int = 0):
         """Device pointers, asynchronous: d_field[r] = the [2, m*m] field (u_rho, u_z) of candidate
-        d_list[r] (d_list = 0: candidate r) of the resident programs; optionally n_finite per row."""
+        d_list[r] (d_list = 0: candidate r) of the resident programs; optionally n_finite per row
+        (required with ``FOL_CPLX`` in the flags: the complex pass selects its rows by it)."""
         prm = params if params is not None else default_fol_params()
         _check(self.h, self.lib.pdeval_gradient_fields(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
                                                        C.byref(prm), d_field, d_n_finite or None, stream or None))

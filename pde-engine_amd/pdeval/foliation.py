@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import FOL_AXIS, FOL_LINK, FOL_MAX_PROBES, FolParams, default_fol_params, fol_params  # noqa: F401
+from ._lib import FOL_AXIS, FOL_CPLX, FOL_LINK, FOL_MAX_PROBES, FolParams, default_fol_params, fol_params  # noqa: F401
 
 
 @dataclass
@@ -118,7 +118,10 @@ def _device(ctx):
 def gradient_fields(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params: Optional[FolParams] = None):
     """(fields, n_finite): the torch float64 [n_rows, 2, m*m] gradient fields and int32 [n_rows]
     finite counts, on ``ctx``'s device, of the candidates ``idx`` (None: all ``n``) of the resident
-    programs ``d_ops`` / ``d_offsets`` (torch tensors or device addresses)."""
+    programs ``d_ops`` / ``d_offsets`` (torch tensors or device addresses).  With ``FOL_CPLX`` in
+    ``params.flags`` a row that is not real-valued (a complex program, or fewer than ``min_points``
+    real points) holds the real gradient field of the same direction, NaN where its direction is
+    not real (DESIGN.md §14 "Complex-valued rows")."""
     import torch
     prm = params if params is not None else default_fol_params()
     dev = _device(ctx)
@@ -142,7 +145,8 @@ def classify(ctx, d_ops, n_words: int, d_offsets, n: int, accepted_idx,
     ``ctx``'s device (``d_ops`` / ``d_offsets``: torch tensors or device addresses), by
     ``pdeval_foliation_classes``: fields, matches and rounds on the device, only the masks come
     back.  ``leader`` holds candidate indices (entries of ``accepted_idx``); ``n_rounds`` is set
-    on the result."""
+    on the result.  With ``FOL_CPLX`` in ``params.flags`` the complex-valued rows are classified
+    too (:func:`gradient_fields`)."""
     import torch
     dev = _device(ctx)
     idx = np.ascontiguousarray(accepted_idx, dtype=np.int64)
@@ -205,7 +209,8 @@ class FoliationRegistry:
     order of creation -- never change.  Assigning a list in any number of consecutive batches
     gives the class ids :func:`classify` gives on the whole list.  Without ``FOL_AXIS`` in the
     flags of ``params`` a function of one coordinate matches nothing, not even itself, so each such
-    row is a leader; with it they form one class per axis.  Calls are synchronous, on the context's stream; close the registry before its
+    row is a leader; with it they form one class per axis.  With ``FOL_CPLX`` :meth:`assign`
+    computes the fields of complex-valued rows as :func:`gradient_fields` does.  Calls are synchronous, on the context's stream; close the registry before its
     context.
 
     The match is not transitive, so two classes can hold the same foliation: their leaders share
@@ -468,7 +473,7 @@ class FoliationRegistry:
         context of the same device, with the same m, grid and flags."""
         if int(other.params.m) != int(self.params.m) or not np.array_equal(other.grid, self.grid):
             raise ValueError('merge: the registries differ in m or grid')
-        if (int(other.params.flags) ^ int(self.params.flags)) & (FOL_AXIS | FOL_LINK):
+        if (int(other.params.flags) ^ int(self.params.flags)) & (FOL_AXIS | FOL_LINK | FOL_CPLX):
             raise ValueError(f'merge: the registries differ in flags ({int(self.params.flags)} here, '
                              f'{int(other.params.flags)} in the other): their classes follow different rules')
         keys, sizes = other._host()
@@ -511,7 +516,7 @@ class FoliationRegistry:
             params.m, params.tau, params.min_points, params.flags = m, tau, min_points, flags
         if int(params.m) != m:
             raise ValueError(f'{path}: m = {m} in the file, {int(params.m)} asked for')
-        if (int(params.flags) ^ flags) & (FOL_AXIS | FOL_LINK):
+        if (int(params.flags) ^ flags) & (FOL_AXIS | FOL_LINK | FOL_CPLX):
             raise ValueError(f'{path}: flags = {flags} in the file, {int(params.flags)} asked for')
         reg = cls(ctx, params, max(capacity_hint, len(keys)))
         try:

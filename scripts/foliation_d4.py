@@ -8,9 +8,14 @@ classification with HIP events (one warm-up run, then the median of --repeats ru
 one JSON object, also written to --out.  With --axis the classification is measured a second
 time in the same process with the axis rule (PDEVAL_FOL_AXIS: the functions of one coordinate
 form one class per axis) and reported under "axis", next to the figures without it; "leader_kinds"
-counts the class leaders that are functions of rho alone or of z alone.
+counts the class leaders that are functions of rho alone or of z alone.  With --cplx it is measured
+once more with PDEVAL_FOL_CPLX (the rows that are not real-valued take the complex field pass)
+under "cplx" (and "axis_cplx"): the rows whose field the complex pass changed (compared on the
+device), the rows its selection rule names (restated on the host), those among the rows
+unclassified without the flag that it classifies, the paper names they join, and the field
+kernels' time with the flag ("field_ms": both kernels) next to "field_kernel_ms" without it.
 
-    python scripts/foliation_d4.py --axis --out foliation_d4.json
+    python scripts/foliation_d4.py --axis --cplx --out foliation_d4.json
 """
 import argparse
 import json
@@ -27,7 +32,7 @@ import torch  # noqa: E402
 from pdeval import foliation as FOL  # noqa: E402
 from pdeval import problem_defs as P  # noqa: E402
 from pdeval._lib import Context, default_fol_params, fol_params  # noqa: E402
-from pdeval.opcodes import CLS_ACCEPT  # noqa: E402
+from pdeval.opcodes import CLS_ACCEPT, FLAG_COMPLEX, MAX_STACK  # noqa: E402
 
 
 def main():
@@ -36,6 +41,7 @@ def main():
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--axis', action='store_true', help='also measure with the axis rule (PDEVAL_FOL_AXIS)')
+    ap.add_argument('--cplx', action='store_true', help='also measure with the complex field pass (PDEVAL_FOL_CPLX)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -58,7 +64,7 @@ def main():
     st = torch.cuda.Stream(dev)
     torch.cuda.synchronize(dev)
 
-    def field_ms():
+    def field_ms(prm=prm):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(st):
             e0.record(st)
@@ -78,7 +84,8 @@ def main():
         return e0.elapsed_time(e1), res
 
     def classes(p):
-        """The classification under parameters p: one warm-up run, then the median of the repeats."""
+        """The classification under parameters p, one warm-up run, then the median of the repeats:
+        (the figures, the FoliationClasses, the tags)."""
         total_ms(p)
         runs = [total_ms(p) for _ in range(a.repeats)]
         leader, n_classes, n_rounds = runs[-1][1]
@@ -99,7 +106,35 @@ def main():
             'total_ms': statistics.median(t for t, _ in runs), 'total_ms_all': [t for t, _ in runs],
             'paper_classes': paper, 'paper_class_counts': paper_n,
             'largest_classes': sorted((int(s) for s in cls.sizes), reverse=True)[:10],
-        }
+        }, cls, tags
+
+    def with_cplx(p, base):
+        """classes(p) for p with FOL_CPLX, and what the complex pass adds to base, the classes of the
+        same parameters without it.  "changed_rows" is observed on the device: the rows whose field
+        bits or n_finite differ between the two field calls (a selected row that is NaN throughout
+        either way does not show).  "selected_rows" restates the kernel's selection rule on the host
+        from the headers and the real pass's counts."""
+        res, cls, tags = classes(p)
+        field_ms(p)
+        c_ms = [field_ms(p) for _ in range(a.repeats)]
+        f0, n0 = FOL.gradient_fields(ctx, d_ops, ops.size, d_off, n, acc, fol_params(p, cplx=False))
+        f1, n1 = FOL.gradient_fields(ctx, d_ops, ops.size, d_off, n, acc, p)
+        changed = (f0.view(torch.int64) != f1.view(torch.int64)).flatten(1).any(1) | (n0 != n1)
+        hdr = ops[off[acc]].astype(np.int64)
+        flagged = (hdr & FLAG_COMPLEX) != 0
+        selected = ((hdr & 0xff) == 0) & (((hdr >> 8) & 0xff) <= MAX_STACK) & \
+            (flagged | (n0.cpu().numpy() < int(p.min_points)))
+        new = (base.class_id < 0) & (cls.class_id >= 0)
+        joined = {}
+        for c in cls.class_id[new]:
+            name = tags.get(int(c), '(unnamed)')
+            joined[name] = joined.get(name, 0) + 1
+        res.update({'field_ms': statistics.median(c_ms), 'field_ms_all': c_ms, 'changed_rows': int(changed.sum()),
+                    'changed_rows_not_selected': int((changed.cpu().numpy() & ~selected).sum()),
+                    'selected_rows': int(selected.sum()), 'flagged_rows': int(flagged.sum()),
+                    'newly_classified': int(new.sum()), 'newly_classified_names': joined,
+                    'new_rows_in_old_classes': int(np.isin(cls.leader[new], base.leader[base.leader >= 0]).sum())})
+        return res
 
     field_ms()
     f_ms = [field_ms() for _ in range(a.repeats)]
@@ -110,9 +145,14 @@ def main():
         'repeats': a.repeats,
         'device': torch.cuda.get_device_name(dev),
     }
-    out.update(classes(fol_params(prm, axis=False)))
+    plain, plain_cls, _ = classes(fol_params(prm, axis=False))
+    out.update(plain)
     if a.axis:
-        out['axis'] = classes(fol_params(prm, axis=True))
+        out['axis'], axis_cls, _ = classes(fol_params(prm, axis=True))
+    if a.cplx:
+        out['cplx'] = with_cplx(fol_params(prm, axis=False, cplx=True), plain_cls)
+        if a.axis:
+            out['axis_cplx'] = with_cplx(fol_params(prm, axis=True, cplx=True), axis_cls)
     ctx.close()
     text = json.dumps(out, indent=1)
     print(text)

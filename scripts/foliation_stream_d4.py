@@ -19,7 +19,9 @@ classes tagged with a paper solution.  With --link (combinable with --axis) the 
 once more with PDEVAL_FOL_LINK under "link" (and "axis_link"): the link pass's device time per batch
 (HIP events around its launches, "link_ms"), the number of links and components, the ten largest
 components, "paper_component_counts" (how many components carry each paper name) and the
-components that hold classes tagged with two different paper names.
+components that hold classes tagged with two different paper names.  With --cplx every measurement
+asked for is repeated with PDEVAL_FOL_CPLX (the rows that are not real-valued take the complex field
+pass) under the same key with "_cplx" appended ("cplx" for the plain one).
 
     python scripts/foliation_stream_d4.py --axis --link --out foliation_stream_d4.json
 """
@@ -49,6 +51,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--axis', action='store_true', help='also measure with the axis rule (PDEVAL_FOL_AXIS)')
     ap.add_argument('--link', action='store_true', help='also measure with the link pass (PDEVAL_FOL_LINK)')
+    ap.add_argument('--cplx', action='store_true', help='also measure with the complex field pass (PDEVAL_FOL_CPLX)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -190,6 +193,12 @@ def main():
         if a.axis:
             out['axis_link'], equal_link = measure(fol_params(prm0, axis=True, link=True))
             equal = equal and equal_link
+    if a.cplx:
+        variants = [('cplx', False, False)] + ([('axis_cplx', True, False)] if a.axis else []) + \
+            ([('link_cplx', False, True)] if a.link else []) + ([('axis_link_cplx', True, True)] if a.axis and a.link else [])
+        for key, axis, link in variants:
+            out[key], equal_cplx = measure(fol_params(prm0, axis=axis, link=link, cplx=True))
+            equal = equal and equal_cplx
     ctx.close()
     text = json.dumps(out)
     print(text)
