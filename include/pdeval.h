@@ -400,6 +400,49 @@ int pdeval_foliation_classes(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_wo
                              int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
                              int64_t* leader, int64_t* n_classes, int32_t* n_rounds);
 
+/* ---- reduction kinds (DESIGN.md §14 "Reduction kinds"): which field lives on a foliation ----
+ * With psi = psi(u) the stream equation becomes psi' A + psi'' B = -I I'(psi), with
+ *   A = (1 - rho^2 w)(u_rr + u_zz) - (1 + rho^2 w) u_r / rho,  B = (1 - rho^2 w)(u_r^2 + u_z^2),
+ * w = omega2 = Omega^2 >= 0.  Along the level sets, T = u_z d_rho - u_r d_z, the right side is
+ * constant: psi' L_T A + psi'' L_T B = 0.  For an accepted u this is consistent, and
+ *   free     L_T A == 0 and L_T B == 0: A and B are functions of u, every psi(u) is a solution;
+ *   vacuum   not free, but W = B L_T A - A L_T B == 0: psi'' / psi' = -A / B has a current-free
+ *            solution, unique up to an affine map;
+ *   current  W != 0: psi'' = kappa(u) psi' with kappa = -L_T A / L_T B, and the current is
+ *            I I' = G(u) psi', G = W / L_T B.
+ * The kind is that of the class (u -> f(u) does not change it) and depends on Omega.
+ * Per point, from the order-3 jet of u (the first ten coefficients of the validator's jet): A and
+ * B to order 1, L_T A = u_z A_rho - u_r A_z, L_T B likewise, W; each X of the three has a
+ * magnitude shadow S_X, the same expression with every coefficient replaced by its modulus and
+ * every difference by a sum (1 - rho^2 w becomes 1 + rho^2 w), so S_W = S_B S_LA + S_A S_LB.  A
+ * point is finite iff the ten coefficients are below 2^160 in modulus and the three X and S_X
+ * are finite; at a finite point X is bad iff |X| > tau S_X.  S_X == 0 is an exact zero: not
+ * bad, still finite.  Per row, over the m x m sample points of the parameters' grid (as
+ * pdeval_gradient_fields), counts = {n_finite, bad_LA, bad_LB, bad_W}, and the first case that
+ * applies decides:
+ *   PDEVAL_RED_NONE     n_finite < min_points, or the whole row is undefined: a program with
+ *                       PDEVAL_FLAG_COMPLEX, one the interpreter declines, offsets or a list
+ *                       entry out of range (never dereferenced) -- as pdeval_gradient_fields;
+ *   PDEVAL_RED_FREE     bad_LA == 0 and bad_LB == 0;
+ *   PDEVAL_RED_VACUUM   bad_W == 0;
+ *   PDEVAL_RED_CURRENT  otherwise.
+ * The kind means something for accepted rows; for any other row it is what the rule gives.
+ * params->flags are ignored (complex-valued rows get PDEVAL_RED_NONE).
+ * Device pointers, asynchronous on `stream` (NULL = the context's).  d_kind (uint8, n_list) is
+ * required; each of the others may be NULL: d_counts int32 [n_list][4]; d_qmax double
+ * [n_list][3], the row maxima of |X| / S_X over the finite points (a diagnostic; 0 at an exact
+ * zero); d_table double [n_list][3][m^2]: per point u, kappa and G -- all three NaN where the
+ * point is not finite, kappa and G also NaN where L_T B is not bad (indistinguishable from zero:
+ * throughout a free row).  G of a vacuum row is rounding noise; it is not clamped.
+ * PDEVAL_ERR_ARG: a Kerr context, omega2 negative or not finite, m outside [4, 64].            */
+#define PDEVAL_RED_NONE 0
+#define PDEVAL_RED_FREE 1
+#define PDEVAL_RED_VACUUM 2
+#define PDEVAL_RED_CURRENT 3
+int pdeval_fol_reduce(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets, int64_t n,
+                      const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params, double omega2,
+                      uint8_t* d_kind, int32_t* d_counts, double* d_qmax, double* d_table, void* stream);
+
 /* ---- foliation class registry (DESIGN.md §14 "Registry"): classes across batches ----
  * A registry keeps the class leaders' gradient fields resident on the device, so a stream of
  * batches is classified as one list: the sequential rule above over the concatenation of all

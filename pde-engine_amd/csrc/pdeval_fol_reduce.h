@@ -1,0 +1,139 @@
+// pdeval_fol_reduce.h -- the reduction kind of a force-free foliation (DESIGN.md §14 "Reduction
+// kinds"): which field lives on the level sets of an accepted u.
+//
+// With psi = psi(u) the stream equation becomes  psi' A + psi'' B = -I I'(psi), where
+//   A = (1 - rho^2 w)(u_rr + u_zz) - (1 + rho^2 w) u_r / rho,   B = (1 - rho^2 w)(u_r^2 + u_z^2),
+// w = Omega^2 (validator.py:323-332).  The right side is a function of u alone, so the derivative
+// along the level sets, L_T = u_z d_rho - u_r d_z, annihilates it:  psi' L_T A + psi'' L_T B = 0.
+// The validator's determinant says that this has a solution psi(u); the three quantities
+//   L_T A,   L_T B,   W = B L_T A - A L_T B
+// say which:
+//   free     L_T A == 0 and L_T B == 0: A and B are functions of u alone, every psi(u) solves the
+//            equation and the current is whatever -(psi' A + psi'' B) gives;
+//   vacuum   not free, W == 0: L_T(A / B) = 0, and psi'' / psi' = -A / B has a current-free
+//            solution, unique up to an affine map;
+//   current  W != 0: psi is fixed by psi'' / psi' = kappa = -L_T A / L_T B and carries the current
+//            I I' = G psi',  G = W / L_T B
+//            (psi' A + psi'' B = psi' (A + kappa B) = psi' (A L_T B - B L_T A) / L_T B = -G psi').
+// The kind does not change under u -> f(u): it is a property of the class.  It depends on Omega.
+//
+// This header holds the per-point rule, which also compiles for the host under -DPD_HOST_SIM
+// (tests/hostsim/sim_fol_reduce.cpp), the kernel's argument block and its launcher.
+#pragma once
+#include "pdeval_foliation.h"
+
+namespace pd {
+
+// ---------------------------------------------------------------- the per-point rule (host + device)
+// From the order-3 jet of u (ten Taylor coefficients c[ji(i, j)]), at rho = x, with p = u_rho and
+// q = u_z as jets (FFEpi::P / Q), lap = u_rr + u_zz and N = p^2 + q^2 to order 1, and the two
+// factors as jets in the rho direction, f = 1 - rho^2 w = (1 - x^2 w, -2 x w) and
+// g = (1 + rho^2 w) / rho = (1/x + x w, w - 1/x^2):
+//   A = f lap - g p,  B = f N                                (order 1: A00, A10, A01)
+//   L_T A = q00 A10 - p00 A01,  L_T B = q00 B10 - p00 B01,  W = B00 L_T A - A00 L_T B.
+// Each X of the three has a magnitude shadow S_X: the same expression on |c_ij| with every factor
+// replaced by its modulus and every difference by a sum (f -> (1 + x^2 w, 2 x w),
+// g -> (1/|x| + |x| w, w + 1/x^2)), the MAG = true evaluation of FFEpi; S_W = S_B S_LA + S_A S_LB.
+// The point is finite iff the ten coefficients pass jet_coef_ok and the three X and the three S_X
+// are finite.  At a finite point X is bad iff |X| > tau S_X (no division); S_X == 0 is an exact
+// zero, not bad, and the point still counts (u = z: L_T B = 0 exactly).
+// Contraction is off and every product is rounded on its own, so a host build computes the same
+// doubles as the device.
+enum { RED_LA = 0, RED_LB = 1, RED_W = 2 };
+struct RedPoint {
+    double X[3], S[3];
+    bool fin;
+    bool bad[3];
+};
+template <bool MAG>
+PD_HD void red_forms(const double* u, double x, double w, double* X) {
+#pragma clang fp contract(off)
+    using E = FFEpi<double, MAG>;
+    const double x2w = (x * x) * w, r0 = 1.0 / x;
+    const double f0 = MAG ? 1.0 + x2w : 1.0 - x2w;
+    const double f1 = (MAG ? 2.0 : -2.0) * (MAG ? fabs(x) : x) * w;
+    const double g0 = MAG ? fabs(r0) + fabs(x) * w : r0 + x * w;
+    const double g1 = MAG ? w + r0 * r0 : w - r0 * r0;
+    const double p00 = E::P(u, 0, 0), p10 = E::P(u, 1, 0), p01 = E::P(u, 0, 1);
+    const double q00 = E::Q(u, 0, 0), q10 = E::Q(u, 1, 0), q01 = E::Q(u, 0, 1);
+    // lap_ij = (i+1)(i+2) c_{i+2,j} + (j+1)(j+2) c_{i,j+2}
+    const double l00 = E::U(u, 2, 0) * 2.0 + E::U(u, 0, 2) * 2.0;
+    const double l10 = E::U(u, 3, 0) * 6.0 + E::U(u, 1, 2) * 2.0;
+    const double l01 = E::U(u, 2, 1) * 2.0 + E::U(u, 0, 3) * 6.0;
+    const double A00 = f0 * l00 + E::sgn(g0 * p00);
+    const double A10 = (f0 * l10 + f1 * l00) + E::sgn(g0 * p10 + g1 * p00);
+    const double A01 = f0 * l01 + E::sgn(g0 * p01);
+    const double n00 = p00 * p00 + q00 * q00;
+    const double n10 = 2.0 * (p00 * p10 + q00 * q10);
+    const double n01 = 2.0 * (p00 * p01 + q00 * q01);
+    const double B00 = f0 * n00, B10 = f0 * n10 + f1 * n00, B01 = f0 * n01;
+    X[RED_LA] = q00 * A10 + E::sgn(p00 * A01);
+    X[RED_LB] = q00 * B10 + E::sgn(p00 * B01);
+    X[RED_W] = B00 * X[RED_LA] + E::sgn(A00 * X[RED_LB]);
+}
+PD_HD RedPoint red_point(const double* u, double x, double w, double tau) {
+#pragma clang fp contract(off)
+    RedPoint r;
+    red_forms<false>(u, x, w, r.X);
+    red_forms<true>(u, x, w, r.S);
+    r.fin = true;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) r.fin = r.fin && fabs(u[i]) < kHugeJet;   // jet_coef_ok
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.fin = r.fin && finite_(r.X[k]) && finite_(r.S[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.bad[k] = r.fin && fabs(r.X[k]) > tau * r.S[k];
+    return r;
+}
+// the diagnostic |X| / S_X of a finite point (IEEE division); 0 at an exact zero, never 0 / 0
+PD_HD double red_q(const RedPoint& r, int k) { return r.S[k] > 0.0 ? fabs(r.X[k]) / r.S[k] : 0.0; }
+// the coefficient functions of the reduced ODE at a point: kappa and G, NaN unless the point is
+// finite and L_T B is bad (distinguishable from zero); G is not clamped
+PD_HD void red_coefs(const RedPoint& r, double& kappa, double& G) {
+    const double nan = __builtin_nan("");
+    const bool ok = r.fin && r.bad[RED_LB];
+    kappa = ok ? -r.X[RED_LA] / r.X[RED_LB] : nan;
+    G = ok ? r.X[RED_W] / r.X[RED_LB] : nan;
+}
+
+// ---------------------------------------------------------------- the per-row rule (host + device)
+// counts: {n_finite, bad_LA, bad_LB, bad_W} over the m x m sample points; the first case decides
+struct RedCount {
+    int n_fin, bad[3];
+};
+PD_HD int red_kind_of(const RedCount& n, int min_points) {
+    if (n.n_fin < min_points) return PDEVAL_RED_NONE;
+    if (n.bad[RED_LA] == 0 && n.bad[RED_LB] == 0) return PDEVAL_RED_FREE;
+    if (n.bad[RED_W] == 0) return PDEVAL_RED_VACUUM;
+    return PDEVAL_RED_CURRENT;
+}
+
+// The operand stack of one wave in order-3 jets: (MAXD - 1) x 10 x 64 doubles.  Two
+// instantiations (DESIGN.md §14 "Reduction kinds"): the shallow one takes the programs whose
+// header names a stack of at most kRedShallowD, the deep one the others up to kFolMaxD.
+constexpr int kRedShallowD = 3;
+template <int MAXD> constexpr int red_stack_doubles() { return (MAXD - 1) * nc(3) * 64; }
+
+#ifndef PD_HOST_SIM
+struct FolReduceArgs {
+    const int32_t* ops;
+    int64_t n_words;
+    const int64_t* offsets;
+    int64_t n;
+    const int64_t* list;       // optional: row -> candidate index (NULL = identity)
+    int64_t n_list;
+    int n_chunk;               // ceil(m^2 / 64)
+    FolGrid grid;
+    PrmTab<double> prm;        // default (all 0): force-free programs carry no problem constants
+    double omega2, tau;
+    int min_points;
+    uint8_t* kind;             // n_list
+    int32_t* counts;           // optional, [n_list][4]
+    double* qmax;              // optional, [n_list][3]
+    double* table;             // optional, [n_list][3][m^2]: u, kappa, G
+};
+// both instantiations, the shallow one first, on s
+void launch_fol_reduce(const FolReduceArgs& a, hipStream_t s);
+#endif  // PD_HOST_SIM
+
+}  // namespace pd

@@ -159,6 +159,51 @@ def classify(ctx, d_ops, n_words: int, d_offsets, n: int, accepted_idx,
     return cls
 
 
+# pdeval_fol_reduce (include/pdeval.h, DESIGN.md §14 "Reduction kinds"): PDEVAL_RED_*
+RED_NONE, RED_FREE, RED_VACUUM, RED_CURRENT = 0, 1, 2, 3
+KIND_NAMES = ('none', 'free', 'vacuum', 'current')
+
+
+def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params: Optional[FolParams] = None,
+                  omega2: float = 0.0, table: bool = False):
+    """The reduction of the stream equation on each foliation: ``(kind, counts, qmax, table)`` of
+    the candidates ``idx`` (None: all ``n``) of the resident programs ``d_ops`` / ``d_offsets``
+    (torch tensors or device addresses) at ``Omega**2 = omega2``, by ``pdeval_fol_reduce``.
+    ``kind`` uint8[rows] indexes ``KIND_NAMES``: free (every ``psi(u)`` solves the equation),
+    vacuum (a current-free ``psi(u)`` exists), current (``psi`` is fixed and carries current) or
+    none (too few finite points, a complex-valued or declined program).  ``counts`` int32[rows, 4]
+    = n_finite, bad_LA, bad_LB, bad_W; ``qmax`` float64[rows, 3] the row maxima of ``|X| / S_X``.
+    ``table`` (a torch float64 [rows, 3, m*m] tensor on the device, or None): ``u``, ``kappa`` and
+    ``G`` at the sample points -- ``psi'' = kappa(u) psi'`` and ``I I' = G(u) psi'`` -- NaN where
+    ``L_T B`` is indistinguishable from zero."""
+    import torch
+    prm = params if params is not None else default_fol_params()
+    dev = _device(ctx)
+    rows = n if idx is None else len(idx)
+    mm = int(prm.m) * int(prm.m)
+    st = torch.cuda.Stream(dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(st):
+        d_list = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+        kind = torch.zeros(rows, dtype=torch.uint8, device=dev)
+        counts = torch.zeros((rows, 4), dtype=torch.int32, device=dev)
+        qmax = torch.zeros((rows, 3), dtype=torch.float64, device=dev)
+        tab = torch.empty((rows, 3, mm), dtype=torch.float64, device=dev) if table else None
+        ctx.fol_reduce(_ptr(d_ops), n_words, _ptr(d_offsets), n, 0 if d_list is None else d_list.data_ptr(), rows,
+                       kind.data_ptr(), omega2, counts.data_ptr(), qmax.data_ptr(), tab.data_ptr() if table else 0,
+                       prm, st.cuda_stream)
+    st.synchronize()
+    return kind.cpu().numpy(), counts.cpu().numpy(), qmax.cpu().numpy(), tab
+
+
+def class_kinds(class_id, kind) -> dict:
+    """{class id: sorted tuple of the kinds its members carry} for the classified rows
+    (``class_id >= 0``); the kind is a property of the class, so a tuple of more than one entry
+    is a class whose members disagree."""
+    class_id, kind = np.asarray(class_id), np.asarray(kind)
+    return {int(c): tuple(int(k) for k in np.unique(kind[class_id == c])) for c in np.unique(class_id[class_id >= 0])}
+
+
 def tag_known(ctx, pd_, classes: FoliationClasses, fields_or_programs, params: Optional[FolParams] = None):
     """The known-solution tag: {class_id: name} of the classes whose leader matches one of
     ``pd_.known_solutions``.  The known solutions are compiled and their fields computed by the

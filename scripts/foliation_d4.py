@@ -14,8 +14,12 @@ under "cplx" (and "axis_cplx"): the rows whose field the complex pass changed (c
 device), the rows its selection rule names (restated on the host), those among the rows
 unclassified without the flag that it classifies, the paper names they join, and the field
 kernels' time with the flag ("field_ms": both kernels) next to "field_kernel_ms" without it.
+With --reduce the reduction kinds of the accepted rows (pdeval_fol_reduce, Omega = 0) are reported
+under "reduce": their histogram, the kind of each class tagged with a paper name, the classes whose
+members disagree (with a few of their rows as examples) and the kernels' time -- against the classes
+of the axis rule when --axis is given, otherwise the plain ones.
 
-    python scripts/foliation_d4.py --axis --cplx --out foliation_d4.json
+    python scripts/foliation_d4.py --axis --cplx --reduce --out foliation_d4.json
 """
 import argparse
 import json
@@ -42,6 +46,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--axis', action='store_true', help='also measure with the axis rule (PDEVAL_FOL_AXIS)')
     ap.add_argument('--cplx', action='store_true', help='also measure with the complex field pass (PDEVAL_FOL_CPLX)')
+    ap.add_argument('--reduce', action='store_true', help='also report the reduction kinds (pdeval_fol_reduce)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -136,6 +141,49 @@ def main():
                     'new_rows_in_old_classes': int(np.isin(cls.leader[new], base.leader[base.leader >= 0]).sum())})
         return res
 
+    def reduce(cls, tags):
+        """The reduction kinds of the accepted rows against the classes cls: one warm-up run, then
+        the median of the repeats (both launches of the kernel, counts and qmax included, no table)."""
+        kind = torch.zeros(len(acc), dtype=torch.uint8, device=dev)
+        counts = torch.zeros((len(acc), 4), dtype=torch.int32, device=dev)
+        qmax = torch.zeros((len(acc), 3), dtype=torch.float64, device=dev)
+
+        def reduce_ms():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(st):
+                e0.record(st)
+                ctx.fol_reduce(d_ops.data_ptr(), ops.size, d_off.data_ptr(), n, d_acc.data_ptr(), len(acc),
+                               kind.data_ptr(), 0.0, counts.data_ptr(), qmax.data_ptr(), 0, prm, st.cuda_stream)
+                e1.record(st)
+            st.synchronize()
+            return e0.elapsed_time(e1)
+
+        reduce_ms()
+        r_ms = [reduce_ms() for _ in range(a.repeats)]
+        k, q = kind.cpu().numpy(), qmax.cpu().numpy()
+        by_class = FOL.class_kinds(cls.class_id, k)
+        mixed = {c: ks for c, ks in by_class.items() if len(ks) > 1}
+        strings = d['exprs'] if 'exprs' in d.files else None
+        examples = {}
+        for c in sorted(mixed, key=lambda c: -int(cls.sizes[c]))[:8]:
+            rows = np.flatnonzero(cls.class_id == c)
+            examples[str(c)] = {
+                'size': int(rows.size), 'tag': tags.get(c),
+                'kinds': {FOL.KIND_NAMES[x]: int((k[rows] == x).sum()) for x in mixed[c]},
+                'rows': [{'candidate': int(acc[r]), 'kind': FOL.KIND_NAMES[int(k[r])], 'qmax': q[r].tolist(),
+                          **({'string': str(strings[acc[r]])} if strings is not None else {})}
+                         for x in mixed[c] for r in rows[k[rows] == x][:2]]}
+        return {
+            'kernel_ms': statistics.median(r_ms), 'kernel_ms_all': r_ms,
+            'kinds': {FOL.KIND_NAMES[x]: int((k == x).sum()) for x in range(4)},
+            'kinds_classified': {FOL.KIND_NAMES[x]: int((k[cls.class_id >= 0] == x).sum()) for x in range(4)},
+            'paper_kinds': {f'{name} ({c})': [FOL.KIND_NAMES[x] for x in by_class[c]] for c, name in sorted(tags.items())},
+            'mixed_classes': len(mixed), 'mixed_examples': examples,
+            # the margin of the rule on this set: the rows' qmax nearest to tau from either side
+            'qmax_below_tau_max': float(q[q <= prm.tau].max(initial=0.0)),
+            'qmax_above_tau_min': float(q[q > prm.tau].min(initial=np.inf)),
+        }
+
     field_ms()
     f_ms = [field_ms() for _ in range(a.repeats)]
     out = {
@@ -145,10 +193,12 @@ def main():
         'repeats': a.repeats,
         'device': torch.cuda.get_device_name(dev),
     }
-    plain, plain_cls, _ = classes(fol_params(prm, axis=False))
+    plain, plain_cls, plain_tags = classes(fol_params(prm, axis=False))
     out.update(plain)
     if a.axis:
-        out['axis'], axis_cls, _ = classes(fol_params(prm, axis=True))
+        out['axis'], axis_cls, axis_tags = classes(fol_params(prm, axis=True))
+    if a.reduce:
+        out['reduce'] = reduce(axis_cls, axis_tags) if a.axis else reduce(plain_cls, plain_tags)
     if a.cplx:
         out['cplx'] = with_cplx(fol_params(prm, axis=False, cplx=True), plain_cls)
         if a.axis:
