@@ -177,8 +177,8 @@ typedef struct pdeval_outputs {
     double*  q_grid;         /* n, max scaled residual q = |res| / S over the finite grid
                                 points.  Kerr: the IEEE quotient of the point with the largest
                                 estimate (its grid-reject text prints it).  Force-free: the
-                                maximum of the estimates |res| * rcp(S) themselves (hardware
-                                reciprocal, ~1 ulp; no reason text reads it), so a diagnostic  */
+                                maximum of |res| * rcp(S) after one Newton step on the quotient,
+                                within about an ulp of the IEEE quotient at every point        */
     int32_t* n_bad;          /* n, grid points that fail the zero test |res| > tau_grid * S
                                 (no division; equal to q > tau_grid except within a rounding
                                 of tau_grid); after tier 2, only points whose residual also

@@ -1045,15 +1045,29 @@ __device__ __forceinline__ double scaled_fast(double res_abs, double S) {
 // oracle (oracle/jet_oracle.c grid_fails) applies the same rule.
 __device__ __forceinline__ bool grid_fails(double res_abs, double S, double tau) { return res_abs > tau * S; }
 
-// a fast estimate of res / S (hardware reciprocal, no refinement): only ORDERS the grid points
-// of a lane for the running maximum of q (GridMax); the reported q is the IEEE quotient of the
-// point it chose
-__device__ __forceinline__ double q_estimate(double res_abs, double S) {
+// the hardware reciprocal of S (no refinement: relative error up to ~2^-27 measured)
+__device__ __forceinline__ double rcp_estimate(double S) {
 #ifndef PD_HOST_SIM
-    return res_abs * __builtin_amdgcn_rcp(S);
+    return __builtin_amdgcn_rcp(S);
 #else
-    return res_abs * (1.0 / S);
+    return 1.0 / S;
 #endif
+}
+
+// a fast estimate of res / S (hardware reciprocal, no refinement): only ORDERS the grid points
+// of a lane for the running maximum of q (GridMax<true>); the reported q is the IEEE quotient
+// of the point it chose
+__device__ __forceinline__ double q_estimate(double res_abs, double S) { return res_abs * rcp_estimate(S); }
+
+// res / S without the division sequence, to about an ulp: the estimate q0 = res * rcp(S) and one
+// Newton step on the quotient, q0 + (res - S q0) * rcp(S) (2 FMA; the estimate's relative error
+// d becomes d^2 ~ 2^-54, plus the last rounding).  Where the step is NaN (S == 0: q0 is inf for
+// res > 0 and NaN for res == 0, as scaled() and GridMax want them; or q0 overflowed) q0 stands.
+__device__ __forceinline__ double q_refined(double res_abs, double S) {
+    const double rc = rcp_estimate(S);
+    const double q0 = res_abs * rc;
+    const double q1 = fma(fma(-S, q0, res_abs), rc, q0);
+    return q1 == q1 ? q1 : q0;
 }
 
 // Per-lane running maximum of the scaled residual q = |res| / S over the finite grid points
@@ -1062,12 +1076,14 @@ __device__ __forceinline__ double q_estimate(double res_abs, double S) {
 // scaled(), so q_grid is that point's IEEE quotient -- the old value wherever the estimates order
 // the points as the quotients do, i.e. unless two quotients of a lane agree to the estimate's
 // accuracy).  res == 0 with S == 0 (estimate NaN) never wins, as q = 0 there; S == 0 with
-// res > 0 (estimate inf) wins, q = inf.  !EXACT (force-free, whose q_grid no reason text
-// reads): the maximum of the estimates themselves, in one register pair instead of three.
+// res > 0 (estimate inf) wins, q = inf.  !EXACT (force-free): the maximum of the refined
+// quotients themselves (q_refined, within about an ulp of each point's IEEE quotient), in one
+// register pair instead of three; a maximum of values, so it does not depend on how the points
+// are split over lanes, waves or passes.
 template <bool EXACT> struct GridMax {
     double r = 0.0, s = 1.0, e = 0.0;
     __device__ __forceinline__ void add(bool finite, double res_abs, double S) {
-        const double est = q_estimate(res_abs, S);
+        const double est = EXACT ? q_estimate(res_abs, S) : q_refined(res_abs, S);
         const bool take = finite & (est > e);
         if constexpr (EXACT) {
             r = take ? res_abs : r;
