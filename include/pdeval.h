@@ -443,6 +443,25 @@ int pdeval_fol_reduce(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, co
                       const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params, double omega2,
                       uint8_t* d_kind, int32_t* d_counts, double* d_qmax, double* d_table, void* stream);
 
+/* ---- the settle tier of the reduction kinds (DESIGN.md §14 "Settled in double-double") ----
+ * pdeval_fol_reduce evaluates in fp64, and a row whose W (or L_T A, L_T B) vanishes identically but
+ * whose jet cancels badly shows |X| / S_X well above tau: functions of rho/z such as
+ * exp(rho/z)/(1 - exp(rho/z)) reach 1e-5 and are called current.  This entry point applies the same
+ * rule to the listed rows with the order-3 jets, L_T A, L_T B and W evaluated in double-double
+ * (~106 bits): the sample points are the same doubles, taken exactly, omega2 is the same double,
+ * immediates that carry PDEVAL_IMM_DD use their low words; the shadows S_X stay fp64 (the moduli
+ * of the coefficients' high parts), and |hi(X)| > tau S_X is bad.  Meant for the few rows whose
+ * fp64 qmax lies in the band between a true zero (<= 1e-12) and a true non-zero (>= 1e-3): the
+ * work is split over the sample points, one wave per (row, 64 points), not over the rows.
+ * Arguments as pdeval_fol_reduce, without a table; d_kind, d_counts ([n_list][4]) and d_qmax
+ * ([n_list][3]) are all required -- the latter two are the accumulators of a row's waves, cleared
+ * by the call -- and hold what pdeval_fol_reduce would write, in the higher precision.  The result
+ * does not depend on the order in which the waves finish.  n_list == 0 is a no-op.
+ * PDEVAL_ERR_ARG: as pdeval_fol_reduce, or a NULL d_kind, d_counts or d_qmax with n_list > 0.     */
+int pdeval_fol_reduce_dd(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
+                         int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
+                         double omega2, uint8_t* d_kind, int32_t* d_counts, double* d_qmax, void* stream);
+
 /* ---- foliation class registry (DESIGN.md §14 "Registry"): classes across batches ----
  * A registry keeps the class leaders' gradient fields resident on the device, so a stream of
  * batches is classified as one list: the sequential rule above over the concatenation of all

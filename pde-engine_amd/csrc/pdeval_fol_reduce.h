@@ -18,7 +18,8 @@
 // The kind does not change under u -> f(u): it is a property of the class.  It depends on Omega.
 //
 // This header holds the per-point rule, which also compiles for the host under -DPD_HOST_SIM
-// (tests/hostsim/sim_fol_reduce.cpp), the kernel's argument block and its launcher.
+// (tests/hostsim/sim_fol_reduce.cpp, sim_fol_reduce_dd.cpp), its double-double twin of the settle
+// tier, the kernels' argument block and their launchers.
 #pragma once
 #include "pdeval_foliation.h"
 
@@ -96,6 +97,62 @@ PD_HD void red_coefs(const RedPoint& r, double& kappa, double& G) {
     G = ok ? r.X[RED_W] / r.X[RED_LB] : nan;
 }
 
+// ---------------------------------------------------------------- the per-point rule in double-double
+// The settle tier (pdeval_fol_reduce_dd): the same rule on an order-3 jet of double-doubles.  X is
+// the expression tree of red_forms<false>, operation for operation, in dd (dd.h); rho is a grid
+// double and enters exactly, Omega^2 is the caller's double.  The shadows stay plain fp64, on the
+// moduli of the coefficients' high parts (they only scale the test: as dd_point_stage does with
+// FFEpi<double, true>).  Finite: the ten |hi(c_i)| below kHugeJet, X (both words) and S finite;
+// bad: |hi(X)| > tau S.  The fp64 functions above are not touched.
+struct RedPointDD {
+    dd X[3];
+    double S[3];
+    bool fin;
+    bool bad[3];
+};
+PD_HD void red_forms_dd(const dd* u, dd x, double w, dd* X) {
+    using E = FFEpi<dd, false>;
+    const dd one = dd_from(1.0);
+    const dd x2w = (x * x) * w, r0 = dd_div(one, x);
+    const dd f0 = one - x2w;
+    const dd f1 = (x * -2.0) * w;
+    const dd g0 = r0 + x * w;
+    const dd g1 = dd_from(w) - r0 * r0;
+    const dd p00 = E::P(u, 0, 0), p10 = E::P(u, 1, 0), p01 = E::P(u, 0, 1);
+    const dd q00 = E::Q(u, 0, 0), q10 = E::Q(u, 1, 0), q01 = E::Q(u, 0, 1);
+    const dd l00 = E::U(u, 2, 0) * 2.0 + E::U(u, 0, 2) * 2.0;
+    const dd l10 = E::U(u, 3, 0) * 6.0 + E::U(u, 1, 2) * 2.0;
+    const dd l01 = E::U(u, 2, 1) * 2.0 + E::U(u, 0, 3) * 6.0;
+    const dd A00 = f0 * l00 - g0 * p00;
+    const dd A10 = (f0 * l10 + f1 * l00) - (g0 * p10 + g1 * p00);
+    const dd A01 = f0 * l01 - g0 * p01;
+    const dd n00 = p00 * p00 + q00 * q00;
+    const dd n10 = (p00 * p10 + q00 * q10) * 2.0;
+    const dd n01 = (p00 * p01 + q00 * q01) * 2.0;
+    const dd B00 = f0 * n00, B10 = f0 * n10 + f1 * n00, B01 = f0 * n01;
+    X[RED_LA] = q00 * A10 - p00 * A01;
+    X[RED_LB] = q00 * B10 - p00 * B01;
+    X[RED_W] = B00 * X[RED_LA] - A00 * X[RED_LB];
+}
+PD_HD RedPointDD red_point_dd(const dd* u, double x, double w, double tau) {
+#pragma clang fp contract(off)
+    RedPointDD r;
+    double m[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) m[i] = mag(u[i]);
+    red_forms_dd(u, dd_from(x), w, r.X);
+    red_forms<true>(m, x, w, r.S);
+    r.fin = true;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) r.fin = r.fin && m[i] < kHugeJet;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.fin = r.fin && finite_(r.X[k]) && finite_(r.S[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.bad[k] = r.fin && fabs(r.X[k].hi) > tau * r.S[k];
+    return r;
+}
+PD_HD double red_q(const RedPointDD& r, int k) { return r.S[k] > 0.0 ? fabs(r.X[k].hi) / r.S[k] : 0.0; }
+
 // ---------------------------------------------------------------- the per-row rule (host + device)
 // counts: {n_finite, bad_LA, bad_LB, bad_W} over the m x m sample points; the first case decides
 struct RedCount {
@@ -134,6 +191,16 @@ struct FolReduceArgs {
 };
 // both instantiations, the shallow one first, on s
 void launch_fol_reduce(const FolReduceArgs& a, hipStream_t s);
+
+// The settle tier (pdeval_fol_reduce_dd.hip): a.counts and a.qmax are required -- they are the
+// accumulators of a row's waves -- and a.table is not used.  Clears them, runs both
+// instantiations of fol_reduce_dd_kernel, then the finishing kernel, all on s.
+void launch_fol_reduce_dd(const FolReduceArgs& a, hipStream_t s);
 #endif  // PD_HOST_SIM
+
+// The double-double operand stack of one wave: a slot is an order-3 jet of dd per lane,
+// 10 x 64 x 16 bytes; the shallow instantiation keeps its two slots in LDS (20,480 bytes), the
+// deep one its seven in private memory (71,680 bytes of LDS are more than a block may have).
+template <int MAXD> constexpr int red_dd_stack_words() { return (MAXD - 1) * nc(3) * 64; }
 
 }  // namespace pd

@@ -483,24 +483,25 @@ template <class T, int NC, int SLOTS> struct PrivVStack {
 };
 
 // program words [pc, end) at (x, y) in jets over T with coordinates / constants of type V
-// (one candidate per lane: vector loads of the program)
+// (VEC, one candidate per lane: vector loads of the program; VEC = false, one program per wave
+// -- fol_reduce_dd_kernel: the words through the constant address space, scalar loads)
 template <class T, int K, int MAXD, class V> struct ValInterp {
     using O = JetOps<T, K>;
     using J = typename O::J;
-    template <class STK>
+    template <class STK, bool VEC = true>
     static __device__ PD_DD_INLINE_ATTR int run(const int32_t* ops, int pc, int end, V x, V y, J& acc, STK& stk,
                               const PrmTab<V>& P) {
         int d = 0;
         if (pc >= end) return RUN_BAD;
         for (;;) {
-            const uint32_t w = (uint32_t)ops[pc];
+            const uint32_t w = VEC ? (uint32_t)ops[pc] : rd_word(ops + pc);
             const uint32_t op = w & 0xffu;
             V immv = vzero<V>();
             int npc = pc + 1;
             if (op_has_imm(op)) {
                 npc = pc + ((w & PDEVAL_IMM_DD) ? 5 : 3);
                 if (npc > end) return RUN_BAD;
-                immv = read_imm<V, true>(ops + pc + 1, w, P);
+                immv = read_imm<V, VEC>(ops + pc + 1, w, P);
             }
             switch (op) {
                 case PDOP_PUSH_X: case PDOP_PUSH_Y: case PDOP_PUSH_C: case PDOP_PUSH_I:

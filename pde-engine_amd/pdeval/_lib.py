@@ -32,7 +32,7 @@ EXPORTS = (
     'pdeval_fol_registry_create', 'pdeval_fol_registry_destroy', 'pdeval_fol_registry_assign',
     'pdeval_fol_registry_assign_fields', 'pdeval_fol_registry_size', 'pdeval_fol_registry_leaders',
     'pdeval_fol_registry_load', 'pdeval_fol_registry_info', 'pdeval_fol_registry_add_sizes',
-    'pdeval_field_kinds', 'pdeval_fol_registry_kinds', 'pdeval_fol_reduce',
+    'pdeval_field_kinds', 'pdeval_fol_registry_kinds', 'pdeval_fol_reduce', 'pdeval_fol_reduce_dd',
     'pdeval_fol_registry_link_fields', 'pdeval_fol_registry_components', 'pdeval_fol_registry_links',
     'pdeval_fol_registry_load_links', 'pdeval_fol_registry_merge_links', 'pdeval_fol_registry_link_ms',
 )
@@ -152,6 +152,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_field_kinds.argtypes = [vp, vp, i64, C.POINTER(FolParams), vp, vp]
     lib.pdeval_fol_registry_kinds.argtypes = [vp, vp]
     lib.pdeval_fol_reduce.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), dbl, vp, vp, vp, vp, vp]
+    lib.pdeval_fol_reduce_dd.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), dbl, vp, vp, vp, vp]
     lib.pdeval_fol_registry_link_fields.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
     lib.pdeval_fol_registry_components.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     lib.pdeval_fol_registry_links.argtypes = [vp, vp]
@@ -399,6 +400,17 @@ class Context:
         _check(self.h, self.lib.pdeval_fol_reduce(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
                                                   C.byref(prm), float(omega2), d_kind or None, d_counts or None,
                                                   d_qmax or None, d_table or None, stream or None))
+
+    def fol_reduce_dd(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int, d_kind: int,
+                      d_counts: int, d_qmax: int, omega2: float = 0.0, params: Optional[FolParams] = None,
+                      stream: int = 0):
+        """Device pointers, asynchronous: the rule of ``fol_reduce`` on the listed candidates with the
+        jets and the three forms evaluated in double-double (pdeval_fol_reduce_dd): d_kind uint8
+        [n_list], d_counts int32 [n_list, 4] and d_qmax float64 [n_list, 3], all three required."""
+        prm = params if params is not None else default_fol_params()
+        _check(self.h, self.lib.pdeval_fol_reduce_dd(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
+                                                     C.byref(prm), float(omega2), d_kind or None, d_counts or None,
+                                                     d_qmax or None, stream or None))
 
     def fol_registry(self, params: Optional[FolParams] = None, capacity_hint: int = 0):
         """A ``pdeval.foliation.FoliationRegistry`` on this context: the class leaders' fields

@@ -854,14 +854,16 @@ class BatchValidator:
             tags = F.tag_known(self.ctx, self.pd, classes, (d_ops, n_words, d_off, n), params)
         return classes, accepted, tags
 
-    def reduction_kinds(self, strings: Sequence[str], omega=0, table: bool = False, params=None):
+    def reduction_kinds(self, strings: Sequence[str], omega=0, table: bool = False, params=None, settle=None):
         """The reduction kind of every candidate among ``strings`` (force-free; DESIGN.md §14
         "Reduction kinds"): which field lives on the foliation -- ``pdeval.foliation.KIND_NAMES``.
         Compiles the strings, uploads the programs once and runs ``pdeval.foliation.reduce_stream``
         on all of them (the kind means something for the accepted ones).  Omega**2 is this
         validator's own when it was created with an Omega, otherwise that of ``omega`` (a
         constant whose square is rational, as the constructor's).  Returns ``(kind, counts, qmax,
-        table)`` in the order of ``strings``; ``table`` is None unless asked for."""
+        table)`` in the order of ``strings``; ``table`` is None unless asked for.  ``settle=(lo, hi)``
+        re-evaluates in double-double the rows whose fp64 ``qmax`` falls in that band and appends
+        their positions to the result (``reduce_stream``)."""
         if self.pd.problem_id != PROBLEM_FORCE_FREE:
             raise ValueError('reduction kinds are a force-free notion (they reduce the stream equation on a '
                              'foliation)')
@@ -874,7 +876,7 @@ class BatchValidator:
         d_ops = torch.from_numpy(np.ascontiguousarray(ops, dtype=np.int32)).to(dev)
         d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64)).to(dev)
         with self._lock:
-            return F.reduce_stream(self.ctx, d_ops, int(d_ops.numel()), d_off, len(off) - 1, None, params, w, table)
+            return F.reduce_stream(self.ctx, d_ops, int(d_ops.numel()), d_off, len(off) - 1, None, params, w, table, settle)
 
     def foliation_registry(self, params=None, capacity_hint: int = 0, axis=None, link=None, cplx=None):
         """A ``pdeval.foliation.FoliationRegistry`` on this validator's context (force-free): the

@@ -165,7 +165,7 @@ KIND_NAMES = ('none', 'free', 'vacuum', 'current')
 
 
 def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params: Optional[FolParams] = None,
-                  omega2: float = 0.0, table: bool = False):
+                  omega2: float = 0.0, table: bool = False, settle=None):
     """The reduction of the stream equation on each foliation: ``(kind, counts, qmax, table)`` of
     the candidates ``idx`` (None: all ``n``) of the resident programs ``d_ops`` / ``d_offsets``
     (torch tensors or device addresses) at ``Omega**2 = omega2``, by ``pdeval_fol_reduce``.
@@ -175,7 +175,15 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
     = n_finite, bad_LA, bad_LB, bad_W; ``qmax`` float64[rows, 3] the row maxima of ``|X| / S_X``.
     ``table`` (a torch float64 [rows, 3, m*m] tensor on the device, or None): ``u``, ``kappa`` and
     ``G`` at the sample points -- ``psi'' = kappa(u) psi'`` and ``I I' = G(u) psi'`` -- NaN where
-    ``L_T B`` is indistinguishable from zero."""
+    ``L_T B`` is indistinguishable from zero.
+
+    ``settle=(lo, hi)`` adds the double-double tier (DESIGN.md §14 "Settled in double-double"): the
+    rows where some ``qmax[k]`` of the fp64 pass lies strictly between ``lo`` and ``hi`` -- neither
+    a clear zero nor a clear non-zero; ``(1e-12, 1e-3)`` is the band of §14 -- are selected on the
+    device, evaluated again by ``pdeval_fol_reduce_dd`` and their kind, counts and qmax replaced by
+    its results; every other row and the table keep the fp64 pass's bits.  The result is then the
+    5-tuple ``(kind, counts, qmax, table, settled)``, ``settled`` the int64 positions of the rows
+    that were re-evaluated.  ``settle=None`` is the fp64 pass alone and returns the 4-tuple."""
     import torch
     prm = params if params is not None else default_fol_params()
     dev = _device(ctx)
@@ -192,8 +200,20 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
         ctx.fol_reduce(_ptr(d_ops), n_words, _ptr(d_offsets), n, 0 if d_list is None else d_list.data_ptr(), rows,
                        kind.data_ptr(), omega2, counts.data_ptr(), qmax.data_ptr(), tab.data_ptr() if table else 0,
                        prm, st.cuda_stream)
+        if settle is not None:
+            lo, hi = settle
+            pos = torch.nonzero(((qmax > lo) & (qmax < hi)).any(1)).flatten()
+            if pos.numel():
+                cand = pos if d_list is None else d_list[pos]
+                k2 = torch.empty(pos.numel(), dtype=torch.uint8, device=dev)
+                c2 = torch.empty((pos.numel(), 4), dtype=torch.int32, device=dev)
+                q2 = torch.empty((pos.numel(), 3), dtype=torch.float64, device=dev)
+                ctx.fol_reduce_dd(_ptr(d_ops), n_words, _ptr(d_offsets), n, cand.data_ptr(), pos.numel(),
+                                  k2.data_ptr(), c2.data_ptr(), q2.data_ptr(), omega2, prm, st.cuda_stream)
+                kind[pos], counts[pos], qmax[pos] = k2, c2, q2
     st.synchronize()
-    return kind.cpu().numpy(), counts.cpu().numpy(), qmax.cpu().numpy(), tab
+    out = kind.cpu().numpy(), counts.cpu().numpy(), qmax.cpu().numpy(), tab
+    return out if settle is None else out + (pos.cpu().numpy(),)
 
 
 def class_kinds(class_id, kind) -> dict:

@@ -17,9 +17,12 @@ kernels' time with the flag ("field_ms": both kernels) next to "field_kernel_ms"
 With --reduce the reduction kinds of the accepted rows (pdeval_fol_reduce, Omega = 0) are reported
 under "reduce": their histogram, the kind of each class tagged with a paper name, the classes whose
 members disagree (with a few of their rows as examples) and the kernels' time -- against the classes
-of the axis rule when --axis is given, otherwise the plain ones.
+of the axis rule when --axis is given, otherwise the plain ones.  With --settle as well, the rows whose
+fp64 |X| / S_X falls between 1e-12 and 1e-3 are evaluated again in double-double
+(pdeval_fol_reduce_dd) and reported under "reduce"/"settle": how many, their kinds before and after,
+the tier's time and the mixed classes before and after.
 
-    python scripts/foliation_d4.py --axis --cplx --reduce --out foliation_d4.json
+    python scripts/foliation_d4.py --axis --cplx --reduce --settle --out foliation_d4.json
 """
 import argparse
 import json
@@ -38,6 +41,8 @@ from pdeval import problem_defs as P  # noqa: E402
 from pdeval._lib import Context, default_fol_params, fol_params  # noqa: E402
 from pdeval.opcodes import CLS_ACCEPT, FLAG_COMPLEX, MAX_STACK  # noqa: E402
 
+SETTLE_BAND = (1e-12, 1e-3)   # no true zero above, no true non-zero below
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
@@ -47,6 +52,8 @@ def main():
     ap.add_argument('--axis', action='store_true', help='also measure with the axis rule (PDEVAL_FOL_AXIS)')
     ap.add_argument('--cplx', action='store_true', help='also measure with the complex field pass (PDEVAL_FOL_CPLX)')
     ap.add_argument('--reduce', action='store_true', help='also report the reduction kinds (pdeval_fol_reduce)')
+    ap.add_argument('--settle', action='store_true',
+                    help='with --reduce: settle the rows in the band in double-double (pdeval_fol_reduce_dd)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -141,6 +148,47 @@ def main():
                     'new_rows_in_old_classes': int(np.isin(cls.leader[new], base.leader[base.leader >= 0]).sum())})
         return res
 
+    def settle(qmax, cls, k, mixed):
+        """The settle tier on the fp64 pass's qmax (a device tensor; k, mixed: its kinds and the
+        mixed classes before): the rows whose qmax falls in SETTLE_BAND, selected on the device, through
+        pdeval_fol_reduce_dd -- one warm-up run, then the median of the repeats (its four launches)."""
+        pos = torch.nonzero(((qmax > SETTLE_BAND[0]) & (qmax < SETTLE_BAND[1])).any(1)).flatten()
+        cand = d_acc[pos]
+        k2 = torch.zeros(len(pos), dtype=torch.uint8, device=dev)
+        c2 = torch.zeros((len(pos), 4), dtype=torch.int32, device=dev)
+        q2 = torch.zeros((len(pos), 3), dtype=torch.float64, device=dev)
+
+        def settle_ms():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(st):
+                e0.record(st)
+                ctx.fol_reduce_dd(d_ops.data_ptr(), ops.size, d_off.data_ptr(), n, cand.data_ptr(), len(pos),
+                                  k2.data_ptr(), c2.data_ptr(), q2.data_ptr(), 0.0, prm, st.cuda_stream)
+                e1.record(st)
+            st.synchronize()
+            return e0.elapsed_time(e1)
+
+        settle_ms()
+        s_ms = [settle_ms() for _ in range(a.repeats)]
+        rows = pos.cpu().numpy()
+        after = k.copy()
+        after[rows] = k2.cpu().numpy()
+        by_class = FOL.class_kinds(cls.class_id, after)
+        still = sorted(c for c, ks in by_class.items() if len(ks) > 1)
+        strings = d['exprs'] if 'exprs' in d.files else None
+        return {'settle': {
+            'band': list(SETTLE_BAND), 'rows_in_band': int(rows.size), 'settle_ms': statistics.median(s_ms),
+            'settle_ms_all': s_ms,
+            'kinds_before': {FOL.KIND_NAMES[x]: int((k[rows] == x).sum()) for x in range(4)},
+            'kinds_after': {FOL.KIND_NAMES[x]: int((after[rows] == x).sum()) for x in range(4)},
+            'rows': [{'candidate': int(acc[r]), 'class': int(cls.class_id[r]), 'before': FOL.KIND_NAMES[int(k[r])],
+                      'after': FOL.KIND_NAMES[int(after[r])], 'qmax_fp64': qmax[r].tolist(), 'qmax_dd': q2[i].tolist(),
+                      **({'string': str(strings[acc[r]])} if strings is not None else {})}
+                     # (the rows whose kind changed first, then those still current, 16 in all)
+                     for i, r in sorted(enumerate(rows), key=lambda t: (k[t[1]] == after[t[1]],
+                                                                        after[t[1]] != FOL.RED_CURRENT))[:16]],
+            'mixed_classes_before': sorted(int(c) for c in mixed), 'mixed_classes_after': [int(c) for c in still]}}
+
     def reduce(cls, tags):
         """The reduction kinds of the accepted rows against the classes cls: one warm-up run, then
         the median of the repeats (both launches of the kernel, counts and qmax included, no table)."""
@@ -173,7 +221,9 @@ def main():
                 'rows': [{'candidate': int(acc[r]), 'kind': FOL.KIND_NAMES[int(k[r])], 'qmax': q[r].tolist(),
                           **({'string': str(strings[acc[r]])} if strings is not None else {})}
                          for x in mixed[c] for r in rows[k[rows] == x][:2]]}
+        settled = settle(qmax, cls, k, mixed) if a.settle else {}
         return {
+            **settled,
             'kernel_ms': statistics.median(r_ms), 'kernel_ms_all': r_ms,
             'kinds': {FOL.KIND_NAMES[x]: int((k == x).sum()) for x in range(4)},
             'kinds_classified': {FOL.KIND_NAMES[x]: int((k[cls.class_id >= 0] == x).sum()) for x in range(4)},
