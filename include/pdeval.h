@@ -427,7 +427,21 @@ int pdeval_foliation_classes(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_wo
  *   PDEVAL_RED_VACUUM   bad_W == 0;
  *   PDEVAL_RED_CURRENT  otherwise.
  * The kind means something for accepted rows; for any other row it is what the rule gives.
- * params->flags are ignored (complex-valued rows get PDEVAL_RED_NONE).
+ * Of params->flags only PDEVAL_FOL_CPLX is read.  With the bit clear complex-valued rows get
+ * PDEVAL_RED_NONE, nothing new is launched and every result is what it was.  With it, after the
+ * real pass and on the same stream, a row the real pass left at PDEVAL_RED_NONE whose list entry,
+ * offsets, header and stack depth pass the checks above -- a program with PDEVAL_FLAG_COMPLEX, or
+ * one that is real at fewer than min_points points: the rows the complex field pass takes -- is
+ * run again in order-3 complex jets, the arithmetic of the validator's complex passes.  If
+ * u = F(g) with g real, L_T A, L_T B and W of u are F'(F' L_T A_g + F'' L_T B_g), F'^3 L_T B_g
+ * and F'^4 W_g, so free, vacuum and current are those of g: the three are evaluated in complex
+ * arithmetic, the shadows S_X on the moduli of the ten coefficients, X is bad iff its modulus
+ * exceeds tau S_X, and a point is finite iff the ten moduli are below 2^160, X (both parts) and
+ * S_X are finite and the point has a real direction by the rule of the complex field pass (above:
+ * |Im t| <= tau |w| |o|), so the kind is defined where the class is (rho + i z has no such point
+ * and stays PDEVAL_RED_NONE).  Such a row's d_kind, d_counts and d_qmax are rewritten; its d_table
+ * rows stay NaN (kappa and G of a complex u are complex); a row the real pass decided keeps every
+ * bit, as does one whose complex run the interpreter declines.
  * Device pointers, asynchronous on `stream` (NULL = the context's).  d_kind (uint8, n_list) is
  * required; each of the others may be NULL: d_counts int32 [n_list][4]; d_qmax double
  * [n_list][3], the row maxima of |X| / S_X over the finite points (a diagnostic; 0 at an exact
@@ -457,6 +471,8 @@ int pdeval_fol_reduce(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, co
  * ([n_list][3]) are all required -- the latter two are the accumulators of a row's waves, cleared
  * by the call -- and hold what pdeval_fol_reduce would write, in the higher precision.  The result
  * does not depend on the order in which the waves finish.  n_list == 0 is a no-op.
+ * params->flags are ignored: a complex-valued row gets PDEVAL_RED_NONE here, also one that
+ * pdeval_fol_reduce gave a kind with PDEVAL_FOL_CPLX -- do not list such rows.
  * PDEVAL_ERR_ARG: as pdeval_fol_reduce, or a NULL d_kind, d_counts or d_qmax with n_list > 0.     */
 int pdeval_fol_reduce_dd(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
                          int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,

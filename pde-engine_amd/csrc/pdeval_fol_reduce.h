@@ -18,8 +18,9 @@
 // The kind does not change under u -> f(u): it is a property of the class.  It depends on Omega.
 //
 // This header holds the per-point rule, which also compiles for the host under -DPD_HOST_SIM
-// (tests/hostsim/sim_fol_reduce.cpp, sim_fol_reduce_dd.cpp), its double-double twin of the settle
-// tier, the kernels' argument block and their launchers.
+// (tests/hostsim/sim_fol_reduce.cpp, sim_fol_reduce_dd.cpp, sim_fol_reduce_cplx.cpp), its
+// double-double twin of the settle tier, its complex twin of the PDEVAL_FOL_CPLX pass, the
+// kernels' argument blocks and their launchers.
 #pragma once
 #include "pdeval_foliation.h"
 
@@ -153,6 +154,69 @@ PD_HD RedPointDD red_point_dd(const dd* u, double x, double w, double tau) {
 }
 PD_HD double red_q(const RedPointDD& r, int k) { return r.S[k] > 0.0 ? fabs(r.X[k].hi) / r.S[k] : 0.0; }
 
+// ---------------------------------------------------------------- the per-point rule of a complex-valued u
+// PDEVAL_FOL_CPLX (pdeval_fol_reduce_cplx.hip; DESIGN.md §14 "Reduction kinds of complex-valued
+// rows").  If u = F(g) with g real and F complex-valued of a real argument, then
+// A_u = F' A_g + F'' B_g, B_u = F'^2 B_g and T_u = F' T_g, hence
+//   L_T A_u = F' (F' L_T A_g + F'' L_T B_g),   L_T B_u = F'^3 L_T B_g,   W_u = F'^4 W_g:
+// the three quantities of u, in complex arithmetic and tested by modulus, vanish where those of g
+// do, and free, vacuum and current carry over.  X is the expression tree of red_forms<false>,
+// operation for operation, on an order-3 jet of cplx; rho and Omega^2 stay real, so the factors
+// f and g are doubles and scale both parts.  The shadows stay plain fp64, red_forms<true> on the
+// moduli m[i] = |c_i| of the coefficients.  Finite: the ten m[i] below kHugeJet, X (both parts)
+// and S finite, and the point has a real direction -- fol_cplx_point(u, u_rho, u_z, tau).fin, the
+// test of the complex field pass, so the kind is defined exactly where the class is
+// (rho + i z has no such point).  Bad: |X| > tau S with |X| the modulus.  The fp64 and dd
+// functions above are not touched.
+struct RedPointCplx {
+    cplx X[3];
+    double S[3];
+    bool fin;
+    bool bad[3];
+};
+PD_HD void red_forms_cplx(const cplx* u, double x, double w, cplx* X) {
+#pragma clang fp contract(off)
+    using E = FFEpi<cplx, false>;
+    const double x2w = (x * x) * w, r0 = 1.0 / x;
+    const double f0 = 1.0 - x2w;
+    const double f1 = -2.0 * x * w;
+    const double g0 = r0 + x * w;
+    const double g1 = w - r0 * r0;
+    const cplx p00 = E::P(u, 0, 0), p10 = E::P(u, 1, 0), p01 = E::P(u, 0, 1);
+    const cplx q00 = E::Q(u, 0, 0), q10 = E::Q(u, 1, 0), q01 = E::Q(u, 0, 1);
+    const cplx l00 = E::U(u, 2, 0) * 2.0 + E::U(u, 0, 2) * 2.0;
+    const cplx l10 = E::U(u, 3, 0) * 6.0 + E::U(u, 1, 2) * 2.0;
+    const cplx l01 = E::U(u, 2, 1) * 2.0 + E::U(u, 0, 3) * 6.0;
+    const cplx A00 = l00 * f0 - p00 * g0;
+    const cplx A10 = (l10 * f0 + l00 * f1) - (p10 * g0 + p00 * g1);
+    const cplx A01 = l01 * f0 - p01 * g0;
+    const cplx n00 = p00 * p00 + q00 * q00;
+    const cplx n10 = (p00 * p10 + q00 * q10) * 2.0;
+    const cplx n01 = (p00 * p01 + q00 * q01) * 2.0;
+    const cplx B00 = n00 * f0, B10 = n10 * f0 + n00 * f1, B01 = n01 * f0;
+    X[RED_LA] = q00 * A10 - p00 * A01;
+    X[RED_LB] = q00 * B10 - p00 * B01;
+    X[RED_W] = B00 * X[RED_LA] - A00 * X[RED_LB];
+}
+PD_HD RedPointCplx red_point_cplx(const cplx* u, double x, double w, double tau) {
+#pragma clang fp contract(off)
+    RedPointCplx r;
+    double m[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) m[i] = mag(u[i]);
+    red_forms_cplx(u, x, w, r.X);
+    red_forms<true>(m, x, w, r.S);
+    r.fin = fol_cplx_point(u[0], u[ji(1, 0)], u[ji(0, 1)], tau).fin;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) r.fin = r.fin && m[i] < kHugeJet;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.fin = r.fin && finite_(r.X[k]) && finite_(r.S[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.bad[k] = r.fin && mag(r.X[k]) > tau * r.S[k];
+    return r;
+}
+PD_HD double red_q(const RedPointCplx& r, int k) { return r.S[k] > 0.0 ? mag(r.X[k]) / r.S[k] : 0.0; }
+
 // ---------------------------------------------------------------- the per-row rule (host + device)
 // counts: {n_finite, bad_LA, bad_LB, bad_W} over the m x m sample points; the first case decides
 struct RedCount {
@@ -196,11 +260,35 @@ void launch_fol_reduce(const FolReduceArgs& a, hipStream_t s);
 // accumulators of a row's waves -- and a.table is not used.  Clears them, runs both
 // instantiations of fol_reduce_dd_kernel, then the finishing kernel, all on s.
 void launch_fol_reduce_dd(const FolReduceArgs& a, hipStream_t s);
+
+// The complex pass (pdeval_fol_reduce_cplx.hip, PDEVAL_FOL_CPLX), after launch_fol_reduce on the
+// same stream: kind is read -- it selects the rows -- and written.  Its own block, so that
+// FolReduceArgs and with it the fp64 kernels' argument layout stay as they are.
+struct FolReduceCplxArgs {
+    const int32_t* ops;
+    int64_t n_words;
+    const int64_t* offsets;
+    int64_t n;
+    const int64_t* list;       // optional: row -> candidate index (NULL = identity)
+    int64_t n_list;
+    int n_chunk;               // ceil(m^2 / 64)
+    FolGrid grid;
+    PrmTab<double> prm;        // default (all 0)
+    double omega2, tau;
+    int min_points;
+    uint8_t* kind;             // n_list, as the real pass left it
+    int32_t* counts;           // optional, [n_list][4]
+    double* qmax;              // optional, [n_list][3]
+};
+// both instantiations, the shallow one first, on s
+void launch_fol_reduce_cplx(const FolReduceCplxArgs& a, hipStream_t s);
 #endif  // PD_HOST_SIM
 
 // The double-double operand stack of one wave: a slot is an order-3 jet of dd per lane,
 // 10 x 64 x 16 bytes; the shallow instantiation keeps its two slots in LDS (20,480 bytes), the
 // deep one its seven in private memory (71,680 bytes of LDS are more than a block may have).
 template <int MAXD> constexpr int red_dd_stack_words() { return (MAXD - 1) * nc(3) * 64; }
+// The complex operand stack has the same shape: a slot is an order-3 jet of cplx per lane.
+template <int MAXD> constexpr int red_cplx_stack_words() { return (MAXD - 1) * nc(3) * 64; }
 
 }  // namespace pd

@@ -1,6 +1,7 @@
 // pdeval_fol_reduce.hip -- the reduction kind of each listed program (DESIGN.md §14 "Reduction
 // kinds"): fol_reduce_kernel and the entry point pdeval_fol_reduce.  Its own unit beside the
-// foliation kernels: nothing of the validation or the class path depends on it.
+// foliation kernels: nothing of the validation or the class path depends on it.  With
+// PDEVAL_FOL_CPLX the entry point then launches the complex pass (pdeval_fol_reduce_cplx.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -135,5 +136,25 @@ extern "C" int pdeval_fol_reduce(pdeval_ctx* c, const int32_t* d_ops, int64_t n_
     a.table = d_table;
     launch_fol_reduce(a, stream ? (hipStream_t)stream : v.stream);
     if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_reduce_kernel", e);
+    if (prm.flags & PDEVAL_FOL_CPLX) {
+        // the rows the real pass left at PDEVAL_RED_NONE, in complex jets (pdeval_fol_reduce_cplx.hip)
+        FolReduceCplxArgs ca{};
+        ca.ops = a.ops;
+        ca.n_words = a.n_words;
+        ca.offsets = a.offsets;
+        ca.n = a.n;
+        ca.list = a.list;
+        ca.n_list = a.n_list;
+        ca.n_chunk = a.n_chunk;
+        ca.grid = a.grid;
+        ca.omega2 = a.omega2;
+        ca.tau = a.tau;
+        ca.min_points = a.min_points;
+        ca.kind = a.kind;
+        ca.counts = a.counts;
+        ca.qmax = a.qmax;
+        launch_fol_reduce_cplx(ca, stream ? (hipStream_t)stream : v.stream);
+        if ((e = hipGetLastError()) != hipSuccess) return fol_hip_fail(c, "fol_reduce_cplx_kernel", e);
+    }
     return PDEVAL_OK;
 }

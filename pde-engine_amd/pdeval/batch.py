@@ -854,7 +854,7 @@ class BatchValidator:
             tags = F.tag_known(self.ctx, self.pd, classes, (d_ops, n_words, d_off, n), params)
         return classes, accepted, tags
 
-    def reduction_kinds(self, strings: Sequence[str], omega=0, table: bool = False, params=None, settle=None):
+    def reduction_kinds(self, strings: Sequence[str], omega=0, table: bool = False, params=None, settle=None, cplx=None):
         """The reduction kind of every candidate among ``strings`` (force-free; DESIGN.md §14
         "Reduction kinds"): which field lives on the foliation -- ``pdeval.foliation.KIND_NAMES``.
         Compiles the strings, uploads the programs once and runs ``pdeval.foliation.reduce_stream``
@@ -863,12 +863,16 @@ class BatchValidator:
         constant whose square is rational, as the constructor's).  Returns ``(kind, counts, qmax,
         table)`` in the order of ``strings``; ``table`` is None unless asked for.  ``settle=(lo, hi)``
         re-evaluates in double-double the rows whose fp64 ``qmax`` falls in that band and appends
-        their positions to the result (``reduce_stream``)."""
+        their positions to the result (``reduce_stream``).  ``cplx=True`` / ``False`` sets / clears
+        ``FOL_CPLX`` in the parameters, as ``foliation_classes`` does: with it the complex-valued rows
+        get a kind too."""
         if self.pd.problem_id != PROBLEM_FORCE_FREE:
             raise ValueError('reduction kinds are a force-free notion (they reduce the stream equation on a '
                              'foliation)')
         import torch
         from . import foliation as F
+        if cplx is not None:
+            params = F.fol_params(params, cplx=cplx)
         from .native import compile_strings
         w = float(self.params.omega2) if float(self.params.omega2) != 0.0 else omega2_value(omega)[0]
         ops, off, _ = compile_strings(self.pd, list(strings))

@@ -183,7 +183,15 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
     device, evaluated again by ``pdeval_fol_reduce_dd`` and their kind, counts and qmax replaced by
     its results; every other row and the table keep the fp64 pass's bits.  The result is then the
     5-tuple ``(kind, counts, qmax, table, settled)``, ``settled`` the int64 positions of the rows
-    that were re-evaluated.  ``settle=None`` is the fp64 pass alone and returns the 4-tuple."""
+    that were re-evaluated.  ``settle=None`` is the fp64 pass alone and returns the 4-tuple.
+
+    With ``FOL_CPLX`` in ``params.flags`` the rows the fp64 pass leaves at none and the complex field
+    pass would take (a complex program, or fewer than ``min_points`` real points) get their kind,
+    counts and qmax from the complex pass (DESIGN.md §14 "Reduction kinds of complex-valued rows");
+    their table rows stay NaN.  Without ``settle`` that is the one call; with it the fp64 pass and
+    the tier run with the flag cleared -- real rows get the same bits with and without the flag --
+    and a second, flagged call then takes the rows still at none that were not settled (the tier is
+    never given a complex row: it would overwrite the kind with none)."""
     import torch
     prm = params if params is not None else default_fol_params()
     dev = _device(ctx)
@@ -197,9 +205,11 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
         counts = torch.zeros((rows, 4), dtype=torch.int32, device=dev)
         qmax = torch.zeros((rows, 3), dtype=torch.float64, device=dev)
         tab = torch.empty((rows, 3, mm), dtype=torch.float64, device=dev) if table else None
+        # with settle the complex pass runs last, on its own call: the fp64 pass and the tier see the flag cleared
+        late_cplx = settle is not None and bool(int(prm.flags) & FOL_CPLX)
         ctx.fol_reduce(_ptr(d_ops), n_words, _ptr(d_offsets), n, 0 if d_list is None else d_list.data_ptr(), rows,
                        kind.data_ptr(), omega2, counts.data_ptr(), qmax.data_ptr(), tab.data_ptr() if table else 0,
-                       prm, st.cuda_stream)
+                       fol_params(prm, cplx=False) if late_cplx else prm, st.cuda_stream)
         if settle is not None:
             lo, hi = settle
             pos = torch.nonzero(((qmax > lo) & (qmax < hi)).any(1)).flatten()
@@ -211,6 +221,15 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
                 ctx.fol_reduce_dd(_ptr(d_ops), n_words, _ptr(d_offsets), n, cand.data_ptr(), pos.numel(),
                                   k2.data_ptr(), c2.data_ptr(), q2.data_ptr(), omega2, prm, st.cuda_stream)
                 kind[pos], counts[pos], qmax[pos] = k2, c2, q2
+            left = kind == RED_NONE
+            left[pos] = False        # (a settled row is real-valued: it keeps the tier's results)
+            none = torch.nonzero(left).flatten() if late_cplx else pos[:0]
+            if none.numel():
+                cand = none if d_list is None else d_list[none]
+                k3, c3, q3 = kind[none], counts[none], qmax[none]      # (copies: a row not taken keeps its bits)
+                ctx.fol_reduce(_ptr(d_ops), n_words, _ptr(d_offsets), n, cand.data_ptr(), none.numel(), k3.data_ptr(),
+                               omega2, c3.data_ptr(), q3.data_ptr(), 0, prm, st.cuda_stream)
+                kind[none], counts[none], qmax[none] = k3, c3, q3
     st.synchronize()
     out = kind.cpu().numpy(), counts.cpu().numpy(), qmax.cpu().numpy(), tab
     return out if settle is None else out + (pos.cpu().numpy(),)

@@ -20,7 +20,9 @@ members disagree (with a few of their rows as examples) and the kernels' time --
 of the axis rule when --axis is given, otherwise the plain ones.  With --settle as well, the rows whose
 fp64 |X| / S_X falls between 1e-12 and 1e-3 are evaluated again in double-double
 (pdeval_fol_reduce_dd) and reported under "reduce"/"settle": how many, their kinds before and after,
-the tier's time and the mixed classes before and after.
+the tier's time and the mixed classes before and after.  With --cplx and --reduce the reduce call is
+repeated with PDEVAL_FOL_CPLX and reported under "cplx"/"reduce" (and "axis_cplx"/"reduce"): the kinds
+of the rows the complex pass took, the classes still mixed and the time of its launches.
 
     python scripts/foliation_d4.py --axis --cplx --reduce --settle --out foliation_d4.json
 """
@@ -146,7 +148,46 @@ def main():
                     'selected_rows': int(selected.sum()), 'flagged_rows': int(flagged.sum()),
                     'newly_classified': int(new.sum()), 'newly_classified_names': joined,
                     'new_rows_in_old_classes': int(np.isin(cls.leader[new], base.leader[base.leader >= 0]).sum())})
+        if a.reduce:
+            res['reduce'] = reduce_cplx(p, cls)
         return res
+
+    def reduce_cplx(p, cls):
+        """pdeval_fol_reduce with FOL_CPLX against the same call without it, on the classes cls of p: the
+        kinds of the rows the complex pass took (the rows whose outputs differ), the classes still mixed
+        or without a kind, and both calls' time -- one warm-up run, then the median of the repeats;
+        "cplx_launch_ms" is their difference, the two launches of fol_reduce_cplx_kernel."""
+        out, ms = {}, {}
+        for name, q in (('off', fol_params(p, cplx=False)), ('on', p)):
+            kind = torch.zeros(len(acc), dtype=torch.uint8, device=dev)
+            counts = torch.zeros((len(acc), 4), dtype=torch.int32, device=dev)
+            qmax = torch.zeros((len(acc), 3), dtype=torch.float64, device=dev)
+            t = []
+            for _ in range(a.repeats + 1):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(st):
+                    e0.record(st)
+                    ctx.fol_reduce(d_ops.data_ptr(), ops.size, d_off.data_ptr(), n, d_acc.data_ptr(), len(acc),
+                                   kind.data_ptr(), 0.0, counts.data_ptr(), qmax.data_ptr(), 0, q, st.cuda_stream)
+                    e1.record(st)
+                st.synchronize()
+                t.append(e0.elapsed_time(e1))
+            ms[name], out[name] = t[1:], (kind.cpu().numpy(), counts.cpu().numpy(), qmax.cpu().numpy())
+        (k0, c0, q0), (k1, c1, q1) = out['off'], out['on']
+        took = (k0 != k1) | (c0 != c1).any(1) | (q0.view(np.int64) != q1.view(np.int64)).any(1)
+        by_class = FOL.class_kinds(cls.class_id, k1)
+        qt = q1[took]
+        return {'reduce_ms': statistics.median(ms['off']), 'reduce_cplx_ms': statistics.median(ms['on']),
+                'cplx_launch_ms': statistics.median(ms['on']) - statistics.median(ms['off']),
+                'reduce_ms_all': ms['off'], 'reduce_cplx_ms_all': ms['on'],
+                'none_without_flag': int((k0 == 0).sum()), 'rows_taken': int(took.sum()),
+                'taken_kinds_before': {FOL.KIND_NAMES[x]: int((k0[took] == x).sum()) for x in range(4)},
+                'taken_kinds': {FOL.KIND_NAMES[x]: int((k1[took] == x).sum()) for x in range(4)},
+                'kinds': {FOL.KIND_NAMES[x]: int((k1 == x).sum()) for x in range(4)},
+                'mixed_classes': sorted(int(c) for c, ks in by_class.items() if len(ks) > 1),
+                'classes_without_kind': sorted(int(c) for c, ks in by_class.items() if ks == (0,)),
+                'taken_qmax_below_tau_max': float(qt[qt <= p.tau].max(initial=0.0)),
+                'taken_qmax_above_tau_min': float(qt[qt > p.tau].min(initial=np.inf))}
 
     def settle(qmax, cls, k, mixed):
         """The settle tier on the fp64 pass's qmax (a device tensor; k, mixed: its kinds and the
