@@ -457,6 +457,29 @@ int pdeval_fol_reduce(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, co
                       const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params, double omega2,
                       uint8_t* d_kind, int32_t* d_counts, double* d_qmax, double* d_table, void* stream);
 
+/* ---- reduction kinds at several rotation rates (DESIGN.md §14 "Reduction kinds at several
+ * rotation rates") ----
+ * The kind depends on Omega (Radial is vacuum at Omega = 0 and current at Omega = 1, z goes from
+ * free to vacuum, rho**2 stays free), but the order-3 jet of u does not: only the per-point rule
+ * reads w = Omega^2.  This entry point interprets each (row, sample point) once and applies the rule
+ * at each of the n_omega values omega2s[0 .. n_omega) (host memory, read before the call returns).
+ * Arguments and nullability as pdeval_fol_reduce; the outputs are Omega-major: d_kind
+ * [n_omega][n_list], d_counts [n_omega][n_list][4], d_qmax [n_omega][n_list][3], d_table
+ * [n_omega][n_list][3][m^2].  Slice k of every output equals, bit for bit (NaNs of the table
+ * included), what pdeval_fol_reduce(..., omega2s[k], ...) writes for the same list, parameters and
+ * flags -- in the real pass and in the PDEVAL_FOL_CPLX pass, which rewrites exactly the slices the
+ * real pass left at PDEVAL_RED_NONE.  Those do not depend on Omega (a declined program, too few
+ * finite jets) unless an Omega^2 is large enough to overflow the forms, so a row is none at every
+ * Omega or at no Omega.  Values may repeat and come in any order.  n_list == 0 is a no-op.  The
+ * settle tier (pdeval_fol_reduce_dd) stays one Omega at a time.
+ * PDEVAL_ERR_ARG: as pdeval_fol_reduce, for every omega2s[k]; n_omega outside
+ * [1, PDEVAL_RED_MAX_OMEGA]; a NULL omega2s.                                                      */
+#define PDEVAL_RED_MAX_OMEGA 8
+int pdeval_fol_reduce_multi(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_words, const int64_t* d_offsets,
+                            int64_t n, const int64_t* d_list, int64_t n_list, const pdeval_fol_params* params,
+                            const double* omega2s /* host, n_omega */, int n_omega,
+                            uint8_t* d_kind, int32_t* d_counts, double* d_qmax, double* d_table, void* stream);
+
 /* ---- the settle tier of the reduction kinds (DESIGN.md §14 "Settled in double-double") ----
  * pdeval_fol_reduce evaluates in fp64, and a row whose W (or L_T A, L_T B) vanishes identically but
  * whose jet cancels badly shows |X| / S_X well above tau: functions of rho/z such as

@@ -33,6 +33,7 @@ EXPORTS = (
     'pdeval_fol_registry_assign_fields', 'pdeval_fol_registry_size', 'pdeval_fol_registry_leaders',
     'pdeval_fol_registry_load', 'pdeval_fol_registry_info', 'pdeval_fol_registry_add_sizes',
     'pdeval_field_kinds', 'pdeval_fol_registry_kinds', 'pdeval_fol_reduce', 'pdeval_fol_reduce_dd',
+    'pdeval_fol_reduce_multi',
     'pdeval_fol_registry_link_fields', 'pdeval_fol_registry_components', 'pdeval_fol_registry_links',
     'pdeval_fol_registry_load_links', 'pdeval_fol_registry_merge_links', 'pdeval_fol_registry_link_ms',
 )
@@ -45,6 +46,7 @@ LIST_NAMES = ('defer_stack3', 'complex', 'defer_stack8', 'tier2', 'tier2_stack3'
               'one_coord')
 N_PASSES = 13
 FOL_MAX_PROBES = 32          # PDEVAL_FOL_MAX_PROBES
+RED_MAX_OMEGA = 8            # PDEVAL_RED_MAX_OMEGA: Omega**2 values of one pdeval_fol_reduce_multi call
 FOL_AXIS = 1                 # PDEVAL_FOL_AXIS: functions of one coordinate form one class per axis
 FOL_LINK = 2                 # PDEVAL_FOL_LINK: a registry records the links between its classes
 FOL_CPLX = 4                 # PDEVAL_FOL_CPLX: rows that are not real-valued take the complex field pass
@@ -152,7 +154,9 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_field_kinds.argtypes = [vp, vp, i64, C.POINTER(FolParams), vp, vp]
     lib.pdeval_fol_registry_kinds.argtypes = [vp, vp]
     lib.pdeval_fol_reduce.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), dbl, vp, vp, vp, vp, vp]
-    lib.pdeval_fol_reduce_dd.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), dbl, vp, vp, vp, vp]
+    lib.pdeval_fol_reduce_multi.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), C.POINTER(dbl), C.c_int,
+                                            vp, vp, vp, vp, vp]
+    lib.pdeval_fol_reduce_dd.argtypes =[vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), dbl, vp, vp, vp, vp]
     lib.pdeval_fol_registry_link_fields.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
     lib.pdeval_fol_registry_components.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     lib.pdeval_fol_registry_links.argtypes = [vp, vp]
@@ -400,6 +404,21 @@ class Context:
         _check(self.h, self.lib.pdeval_fol_reduce(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
                                                   C.byref(prm), float(omega2), d_kind or None, d_counts or None,
                                                   d_qmax or None, d_table or None, stream or None))
+
+    def fol_reduce_multi(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int, d_kind: int,
+                         omega2s, d_counts: int = 0, d_qmax: int = 0, d_table: int = 0,
+                         params: Optional[FolParams] = None, stream: int = 0):
+        """Device pointers, asynchronous: ``fol_reduce`` at each of the 1 .. ``RED_MAX_OMEGA`` values
+        ``omega2s`` (host floats) in one pass that interprets every program once
+        (pdeval_fol_reduce_multi).  The outputs are Omega-major -- d_kind uint8 [K, n_list], counts
+        int32 [K, n_list, 4], qmax float64 [K, n_list, 3], table float64 [K, n_list, 3, m*m] -- and
+        slice k holds the bits ``fol_reduce`` writes at ``omega2s[k]``."""
+        prm = params if params is not None else default_fol_params()
+        w = (C.c_double * len(omega2s))(*(float(v) for v in omega2s))
+        _check(self.h, self.lib.pdeval_fol_reduce_multi(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
+                                                        C.byref(prm), w, len(omega2s), d_kind or None,
+                                                        d_counts or None, d_qmax or None, d_table or None,
+                                                        stream or None))
 
     def fol_reduce_dd(self, d_ops: int, n_words: int, d_offsets: int, n: int, d_list: int, n_list: int, d_kind: int,
                       d_counts: int, d_qmax: int, omega2: float = 0.0, params: Optional[FolParams] = None,

@@ -865,7 +865,9 @@ class BatchValidator:
         re-evaluates in double-double the rows whose fp64 ``qmax`` falls in that band and appends
         their positions to the result (``reduce_stream``).  ``cplx=True`` / ``False`` sets / clears
         ``FOL_CPLX`` in the parameters, as ``foliation_classes`` does: with it the complex-valued rows
-        get a kind too."""
+        get a kind too.  ``omega`` may be a list or tuple of such constants (at most
+        ``RED_MAX_OMEGA``): the programs are then interpreted once for all of them and every result
+        gains a leading axis over ``omega`` (``reduce_stream``; not with ``settle``)."""
         if self.pd.problem_id != PROBLEM_FORCE_FREE:
             raise ValueError('reduction kinds are a force-free notion (they reduce the stream equation on a '
                              'foliation)')
@@ -874,7 +876,10 @@ class BatchValidator:
         if cplx is not None:
             params = F.fol_params(params, cplx=cplx)
         from .native import compile_strings
-        w = float(self.params.omega2) if float(self.params.omega2) != 0.0 else omega2_value(omega)[0]
+        if isinstance(omega, (list, tuple)):     # several Omega in one device pass: results [len(omega), rows, ...]
+            w = [omega2_value(v)[0] for v in omega]
+        else:
+            w = float(self.params.omega2) if float(self.params.omega2) != 0.0 else omega2_value(omega)[0]
         ops, off, _ = compile_strings(self.pd, list(strings))
         dev = torch.device('cuda', self.device)
         d_ops = torch.from_numpy(np.ascontiguousarray(ops, dtype=np.int32)).to(dev)

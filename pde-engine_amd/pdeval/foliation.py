@@ -165,7 +165,7 @@ KIND_NAMES = ('none', 'free', 'vacuum', 'current')
 
 
 def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params: Optional[FolParams] = None,
-                  omega2: float = 0.0, table: bool = False, settle=None):
+                  omega2=0.0, table: bool = False, settle=None):
     """The reduction of the stream equation on each foliation: ``(kind, counts, qmax, table)`` of
     the candidates ``idx`` (None: all ``n``) of the resident programs ``d_ops`` / ``d_offsets``
     (torch tensors or device addresses) at ``Omega**2 = omega2``, by ``pdeval_fol_reduce``.
@@ -191,7 +191,14 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
     their table rows stay NaN.  Without ``settle`` that is the one call; with it the fp64 pass and
     the tier run with the flag cleared -- real rows get the same bits with and without the flag --
     and a second, flagged call then takes the rows still at none that were not settled (the tier is
-    never given a complex row: it would overwrite the kind with none)."""
+    never given a complex row: it would overwrite the kind with none).
+
+    ``omega2`` may be a sequence of up to ``RED_MAX_OMEGA`` values: one ``pdeval_fol_reduce_multi``
+    call then interprets every program once and applies the rule at each value (DESIGN.md §14
+    "Reduction kinds at several rotation rates").  The results gain a leading axis -- ``kind``
+    [K, rows], ``counts`` [K, rows, 4], ``qmax`` [K, rows, 3], ``table`` [K, rows, 3, m*m] -- and
+    slice ``k`` holds the bits of the call with the scalar ``omega2[k]``.  ``settle`` is one
+    Omega at a time: with a sequence it raises ``ValueError``."""
     import torch
     prm = params if params is not None else default_fol_params()
     dev = _device(ctx)
@@ -199,6 +206,21 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
     mm = int(prm.m) * int(prm.m)
     st = torch.cuda.Stream(dev)
     st.wait_stream(torch.cuda.current_stream(dev))
+    if np.ndim(omega2):
+        if settle is not None:
+            raise ValueError('settle takes one Omega at a time: call reduce_stream per value of omega2')
+        ws = [float(w) for w in omega2]
+        with torch.cuda.stream(st):
+            d_list = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+            kind = torch.zeros((len(ws), rows), dtype=torch.uint8, device=dev)
+            counts = torch.zeros((len(ws), rows, 4), dtype=torch.int32, device=dev)
+            qmax = torch.zeros((len(ws), rows, 3), dtype=torch.float64, device=dev)
+            tab = torch.empty((len(ws), rows, 3, mm), dtype=torch.float64, device=dev) if table else None
+            ctx.fol_reduce_multi(_ptr(d_ops), n_words, _ptr(d_offsets), n, 0 if d_list is None else d_list.data_ptr(),
+                                 rows, kind.data_ptr(), ws, counts.data_ptr(), qmax.data_ptr(),
+                                 tab.data_ptr() if table else 0, prm, st.cuda_stream)
+        st.synchronize()
+        return kind.cpu().numpy(), counts.cpu().numpy(), qmax.cpu().numpy(), tab
     with torch.cuda.stream(st):
         d_list = None if idx is None else torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
         kind = torch.zeros(rows, dtype=torch.uint8, device=dev)

@@ -22,7 +22,11 @@ fp64 |X| / S_X falls between 1e-12 and 1e-3 are evaluated again in double-double
 (pdeval_fol_reduce_dd) and reported under "reduce"/"settle": how many, their kinds before and after,
 the tier's time and the mixed classes before and after.  With --cplx and --reduce the reduce call is
 repeated with PDEVAL_FOL_CPLX and reported under "cplx"/"reduce" (and "axis_cplx"/"reduce"): the kinds
-of the rows the complex pass took, the classes still mixed and the time of its launches.
+of the rows the complex pass took, the classes still mixed and the time of its launches.  With --reduce
+and --omega 0,1/2,1 the kinds at each of these rotation rates come from one pdeval_fol_reduce_multi call
+and are reported under "reduce"/"omega": the histogram per Omega, the kinds of each tagged class at each
+Omega, and the call's time next to that of one pdeval_fol_reduce call per value (with --cplx both carry
+PDEVAL_FOL_CPLX).
 
     python scripts/foliation_d4.py --axis --cplx --reduce --settle --out foliation_d4.json
 """
@@ -56,6 +60,9 @@ def main():
     ap.add_argument('--reduce', action='store_true', help='also report the reduction kinds (pdeval_fol_reduce)')
     ap.add_argument('--settle', action='store_true',
                     help='with --reduce: settle the rows in the band in double-double (pdeval_fol_reduce_dd)')
+    ap.add_argument('--omega', default=None,
+                    help='with --reduce: a comma-separated list of at most 8 rotation rates, e.g. 0,1/2,1: the kinds at '
+                         'each of them in one pass (pdeval_fol_reduce_multi)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -275,6 +282,49 @@ def main():
             'qmax_above_tau_min': float(q[q > prm.tau].min(initial=np.inf)),
         }
 
+    def reduce_omega(cls, tags, p):
+        """The reduction kinds at every Omega of --omega in one pdeval_fol_reduce_multi call against one
+        pdeval_fol_reduce call per value, both with counts and qmax and without a table: one warm-up
+        run, then the median of the repeats.  Per Omega the histogram, per tagged class its kinds."""
+        from pdeval.batch import omega2_value
+        names = [s.strip() for s in a.omega.split(',')]
+        ws = [omega2_value(s)[0] for s in names]
+        kind = torch.zeros((len(ws), len(acc)), dtype=torch.uint8, device=dev)
+        counts = torch.zeros((len(ws), len(acc), 4), dtype=torch.int32, device=dev)
+        qmax = torch.zeros((len(ws), len(acc), 3), dtype=torch.float64, device=dev)
+        single = (torch.zeros_like(kind), torch.zeros_like(counts), torch.zeros_like(qmax))
+
+        def call_ms(multi):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(st):
+                e0.record(st)
+                if multi:
+                    ctx.fol_reduce_multi(d_ops.data_ptr(), ops.size, d_off.data_ptr(), n, d_acc.data_ptr(), len(acc),
+                                         kind.data_ptr(), ws, counts.data_ptr(), qmax.data_ptr(), 0, p, st.cuda_stream)
+                else:
+                    for i, w in enumerate(ws):
+                        ctx.fol_reduce(d_ops.data_ptr(), ops.size, d_off.data_ptr(), n, d_acc.data_ptr(), len(acc),
+                                       single[0][i].data_ptr(), w, single[1][i].data_ptr(), single[2][i].data_ptr(), 0,
+                                       p, st.cuda_stream)
+                e1.record(st)
+            st.synchronize()
+            return e0.elapsed_time(e1)
+
+        ms = {}
+        for multi in (True, False):
+            call_ms(multi)
+            ms[multi] = [call_ms(multi) for _ in range(a.repeats)]
+        k = kind.cpu().numpy()
+        same = all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip((kind, counts, qmax), single))
+        by_class = [FOL.class_kinds(cls.class_id, k[i]) for i in range(len(ws))]
+        return {'omega': names, 'omega2': ws, 'flags': int(p.flags),
+                'multi_ms': statistics.median(ms[True]), 'multi_ms_all': ms[True],
+                'single_calls_ms': statistics.median(ms[False]), 'single_calls_ms_all': ms[False],
+                'bits_equal_single_calls': bool(same),
+                'kinds': {s: {FOL.KIND_NAMES[x]: int((k[i] == x).sum()) for x in range(4)} for i, s in enumerate(names)},
+                'paper_kinds': {f'{name} ({c})': {s: [FOL.KIND_NAMES[x] for x in by_class[i][c]] for i, s in enumerate(names)}
+                                for c, name in sorted(tags.items())}}
+
     field_ms()
     f_ms = [field_ms() for _ in range(a.repeats)]
     out = {
@@ -289,7 +339,10 @@ def main():
     if a.axis:
         out['axis'], axis_cls, axis_tags = classes(fol_params(prm, axis=True))
     if a.reduce:
-        out['reduce'] = reduce(axis_cls, axis_tags) if a.axis else reduce(plain_cls, plain_tags)
+        red_cls, red_tags = (axis_cls, axis_tags) if a.axis else (plain_cls, plain_tags)
+        out['reduce'] = reduce(red_cls, red_tags)
+        if a.omega:
+            out['reduce']['omega'] = reduce_omega(red_cls, red_tags, fol_params(prm, cplx=a.cplx))
     if a.cplx:
         out['cplx'] = with_cplx(fol_params(prm, axis=False, cplx=True), plain_cls)
         if a.axis:
