@@ -521,10 +521,18 @@ template <int W> struct PowTab {
 #ifndef PD_PIN_Y
 #define PD_PIN_Y 1
 #endif
+// A register move the force-free interpreter does not need (K = 4, real; scripts/mov_blocks.py
+// lists the moves per basic block): the pinned ordinate (PD_PIN_Y) is carried through the opcode
+// loop and pinned where it lies, instead of being copied from y_in into a fresh register pair
+// at every opcode.  No arithmetic changes (PD_LEAN_MOVES=0: the copy as it was, the A/B variant).
+#ifndef PD_LEAN_MOVES
+#define PD_LEAN_MOVES 1
+#endif
 template <class T, int K, int W, int MAXD> struct Lean {
     using O = JetOps<T, K>;
     using J = typename O::J;
     static constexpr int NCJ = nc(K);
+    static constexpr bool LM = PD_LEAN_MOVES && K == 4 && !Real<T>::cplx_pass;
 
     // Kerr (K = 2): the mixed coefficient u_rx feeds only itself through every jet operation
     // and the operator has no mixed term (kerr_epilogue), so it is not stored, not loaded and
@@ -615,14 +623,21 @@ template <class T, int K, int W, int MAXD> struct Lean {
         double imm = PD_LEAN_IMM_PREFETCH ? rd_imm(dec + pc0 + 1) : 0.0;
         bool first = fresh || pc0 == 1;
         int d = first ? 0 : 1;   // operand stack depth (wave-uniform); MAXD = 2 needs only `first`
+        [[maybe_unused]] double y_lm = y_in;   // (PD_LEAN_MOVES) the ordinate, loop-carried (LM below)
         for (;;) {
             // (PD_PIN_Y) the lane's ordinate made opaque once per opcode: values derived from it
             // (the powers y^k of a coordinate power) are formed where an opcode uses them instead
             // of being hoisted out of the loop and kept live -- spilled to scratch -- through it
             // (force-free only: same box, pass 1 129.4 -> 125.4 ms and its scratch frame 96 -> 64
             // B/lane; Kerr's pass 1 went 48.5 -> 50.0 ms with it, profiles/r06_m_ab_*)
-            double y = y_in;
-            if constexpr (PD_PIN_Y && K == 4) pin_f64(y);
+            double y;
+            if constexpr (LM) {   // the loop-carried copy, pinned where it lies: no move per opcode
+                if constexpr (PD_PIN_Y) pin_f64(y_lm);
+                y = y_lm;
+            } else {
+                y = y_in;
+                if constexpr (PD_PIN_Y && K == 4) pin_f64(y);
+            }
             const uint32_t op = w & 0xffu;
             const uint32_t grp = (w >> 17) & 7u;
             // group tests: a bit test on the one-hot copy (s_bitcmp + branch) or a compare of
