@@ -480,6 +480,36 @@ int pdeval_fol_reduce_multi(pdeval_ctx* ctx, const int32_t* d_ops, int64_t n_wor
                             const double* omega2s /* host, n_omega */, int n_omega,
                             uint8_t* d_kind, int32_t* d_counts, double* d_qmax, double* d_table, void* stream);
 
+/* ---- profiles (DESIGN.md §14 "Profiles: psi(u) and the current"): psi(u) and I(psi) on a foliation ----
+ * The step the table is for: psi'' = kappa(u) psi' and I I'(psi) = G(u) psi' integrated along u.
+ * Each of the n_rows rows of d_table ([n_rows][3][m^2]: u, kappa, G at the sample points p, as
+ * pdeval_fol_reduce writes them; a pdeval_fol_reduce_multi table is n_omega x n_list such rows) is
+ * treated alone:
+ *   valid    p is valid iff u_p, kappa_p and G_p are all finite; n = the number of valid points (a
+ *            free row, whose kappa and G are NaN throughout, has n = 0);
+ *   order    the valid points ascending by u_p + 0.0 (-0.0 and +0.0 are one value), ties by
+ *            ascending p: (u_i, kappa_i, G_i, p_i), i = 0 .. n-1, D_i = u_i - u_{i-1};
+ *   sums     the trapezoid rule, normalised to psi(u_0) = 0, psi'(u_0) = 1 (the affine freedom):
+ *            P_0 = 0,   P_i = P_{i-1} + (kappa_i + kappa_{i-1}) D_i / 2,   psi'_i = exp(P_i),
+ *            psi_0 = 0, psi_i = psi_{i-1} + (psi'_i + psi'_{i-1}) D_i / 2,
+ *            Q_0 = 0,   Q_i = Q_{i-1} + (G_i psi'_i^2 + G_{i-1} psi'_{i-1}^2) D_i / 2,
+ *            Q = (I^2 - I^2(u_0)) / 2, from d(I^2 / 2)/du = I I'(psi) psi' = G psi'^2.  A tie adds
+ *            nothing (D = 0).  Q of a vacuum row is rounding noise, as its G; it is not clamped.  An
+ *            exp that overflows is not special: the row holds inf or NaN where the sums give them.
+ * d_n[row] (int32) = n.  d_profile[row][4][m^2]: u_i (the key: +0.0 for either zero), psi'_i, psi_i
+ * and Q_i at position i < n, NaN at i >= n.  d_perm[row][m^2] (int32): p_i at i < n, -1 at i >= n --
+ * the map back to the (rho, z) sample grid.  With n < min_points the whole profile row is NaN and
+ * the whole perm row -1; d_n still holds n.  Every word of the outputs is written: do not pre-clear.
+ * The sums are parallel prefix sums: they associate differently from a sequential loop and agree
+ * with it to rounding, not to the bit; n, the order and the fill are exact.
+ * Device pointers, asynchronous on `stream` (NULL = the context's).  d_profile is required; d_perm
+ * and d_n may be NULL.  Of params only m and min_points are read.  n_rows == 0 is a no-op.
+ * PDEVAL_ERR_ARG: a Kerr context, m outside [4, 64], min_points < 1, a NULL d_table or d_profile
+ * with n_rows > 0.                                                                               */
+int pdeval_fol_profile(pdeval_ctx* ctx, const double* d_table, int64_t n_rows,
+                       const pdeval_fol_params* params, double* d_profile,
+                       int32_t* d_perm, int32_t* d_n, void* stream);
+
 /* ---- the settle tier of the reduction kinds (DESIGN.md §14 "Settled in double-double") ----
  * pdeval_fol_reduce evaluates in fp64, and a row whose W (or L_T A, L_T B) vanishes identically but
  * whose jet cancels badly shows |X| / S_X well above tau: functions of rho/z such as

@@ -33,7 +33,7 @@ EXPORTS = (
     'pdeval_fol_registry_assign_fields', 'pdeval_fol_registry_size', 'pdeval_fol_registry_leaders',
     'pdeval_fol_registry_load', 'pdeval_fol_registry_info', 'pdeval_fol_registry_add_sizes',
     'pdeval_field_kinds', 'pdeval_fol_registry_kinds', 'pdeval_fol_reduce', 'pdeval_fol_reduce_dd',
-    'pdeval_fol_reduce_multi',
+    'pdeval_fol_reduce_multi', 'pdeval_fol_profile',
     'pdeval_fol_registry_link_fields', 'pdeval_fol_registry_components', 'pdeval_fol_registry_links',
     'pdeval_fol_registry_load_links', 'pdeval_fol_registry_merge_links', 'pdeval_fol_registry_link_ms',
 )
@@ -157,6 +157,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib.pdeval_fol_reduce_multi.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), C.POINTER(dbl), C.c_int,
                                             vp, vp, vp, vp, vp]
     lib.pdeval_fol_reduce_dd.argtypes =[vp, vp, i64, vp, i64, vp, i64, C.POINTER(FolParams), dbl, vp, vp, vp, vp]
+    lib.pdeval_fol_profile.argtypes = [vp, vp, i64, C.POINTER(FolParams), vp, vp, vp, vp]
     lib.pdeval_fol_registry_link_fields.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
     lib.pdeval_fol_registry_components.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64)]
     lib.pdeval_fol_registry_links.argtypes = [vp, vp]
@@ -430,6 +431,17 @@ class Context:
         _check(self.h, self.lib.pdeval_fol_reduce_dd(self.h, d_ops, n_words, d_offsets, n, d_list or None, n_list,
                                                      C.byref(prm), float(omega2), d_kind or None, d_counts or None,
                                                      d_qmax or None, stream or None))
+
+    def fol_profile(self, d_table: int, n_rows: int, d_profile: int, d_perm: int = 0, d_n: int = 0,
+                    params: Optional[FolParams] = None, stream: int = 0):
+        """Device pointers, asynchronous: each row of the table float64 [n_rows, 3, m*m] of
+        ``fol_reduce`` sorted by ``u`` and integrated by the trapezoid rule (pdeval_fol_profile):
+        d_profile float64 [n_rows, 4, m*m] = ``u``, ``psi'``, ``psi`` and ``Q = (I**2 - I0**2)/2`` at the
+        sorted positions, NaN past the row's ``n`` valid points; optionally d_perm int32 [n_rows, m*m],
+        the sample point of each position (-1 past ``n``), and d_n int32 [n_rows]."""
+        prm = params if params is not None else default_fol_params()
+        _check(self.h, self.lib.pdeval_fol_profile(self.h, d_table or None, n_rows, C.byref(prm), d_profile or None,
+                                                   d_perm or None, d_n or None, stream or None))
 
     def fol_registry(self, params: Optional[FolParams] = None, capacity_hint: int = 0):
         """A ``pdeval.foliation.FoliationRegistry`` on this context: the class leaders' fields

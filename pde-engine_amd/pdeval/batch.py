@@ -887,6 +887,18 @@ class BatchValidator:
         with self._lock:
             return F.reduce_stream(self.ctx, d_ops, int(d_ops.numel()), d_off, len(off) - 1, None, params, w, table, settle)
 
+    def reduction_profiles(self, strings: Sequence[str], omega=0, params=None):
+        """``psi(u)`` and the current on the foliation of every candidate among ``strings``
+        (force-free; DESIGN.md §14 "Profiles: psi(u) and the current"): ``reduction_kinds`` with the
+        table, then ``pdeval.foliation.profiles`` on it, the table never leaving the device.
+        Returns ``(kind, profile, perm, n)`` in the order of ``strings``: ``kind`` as
+        ``reduction_kinds`` gives it (numpy), the other three device tensors as ``profiles`` gives
+        them.  ``omega`` as in ``reduction_kinds``; a list or tuple adds a leading axis to all four."""
+        from . import foliation as F
+        kind, _, _, tab = self.reduction_kinds(strings, omega=omega, table=True, params=params)
+        with self._lock:
+            return (kind,) + F.profiles(self.ctx, tab, params)
+
     def foliation_registry(self, params=None, capacity_hint: int = 0, axis=None, link=None, cplx=None):
         """A ``pdeval.foliation.FoliationRegistry`` on this validator's context (force-free): the
         streaming caller holds it next to the validator and passes it to ``assign_foliation``, which

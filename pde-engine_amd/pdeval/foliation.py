@@ -257,6 +257,40 @@ def reduce_stream(ctx, d_ops, n_words: int, d_offsets, n: int, idx=None, params:
     return out if settle is None else out + (pos.cpu().numpy(),)
 
 
+def profiles(ctx, table, params: Optional[FolParams] = None, perm: bool = True):
+    """``psi(u)`` and the current along each foliation: ``(profile, perm, n)`` from the table tensor
+    ``reduce_stream(..., table=True)`` returns -- float64 ``[rows, 3, m*m]`` on ``ctx``'s device, or
+    the ``[K, rows, 3, m*m]`` of a sequence of Omega -- by ``pdeval_fol_profile`` (DESIGN.md §14
+    "Profiles: psi(u) and the current").  Each row's valid points (``u``, ``kappa`` and ``G`` all
+    finite) are sorted by ``u`` and ``psi'' = kappa(u) psi'``, ``I I' = G(u) psi'`` integrated by the
+    trapezoid rule from ``psi = 0``, ``psi' = 1`` at the smallest ``u``.  All three results are torch
+    tensors on the device with the table's leading shape: ``profile`` float64 ``[..., 4, m*m]`` = ``u``,
+    ``psi'``, ``psi`` and ``Q = (I**2 - I0**2) / 2`` at the sorted positions, NaN past the row's ``n``
+    valid points; ``perm`` int32 ``[..., m*m]`` the sample point ``p = i m + j`` of each position, -1
+    past ``n`` (None with ``perm=False``); ``n`` int32 ``[...]``.  A row with ``n < params.min_points``
+    -- every free row -- is NaN / -1 throughout.  Of ``params`` only ``m`` and ``min_points`` are read."""
+    import torch
+    prm = params if params is not None else default_fol_params()
+    dev = _device(ctx)
+    mm = int(prm.m) * int(prm.m)
+    if table.dtype != torch.float64 or table.device != dev or table.dim() < 3 or tuple(table.shape[-2:]) != (3, mm):
+        raise ValueError(f'profiles: expected a float64 [..., 3, {mm}] table on {dev}, got {table.dtype} '
+                         f'{tuple(table.shape)} on {table.device}')
+    lead = tuple(table.shape[:-2])
+    rows = int(np.prod(lead))
+    st = torch.cuda.Stream(dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(st):
+        tab = table.contiguous()
+        prof = torch.empty(lead + (4, mm), dtype=torch.float64, device=dev)
+        prm_ = torch.empty(lead + (mm,), dtype=torch.int32, device=dev) if perm else None
+        cnt = torch.empty(lead, dtype=torch.int32, device=dev)
+        ctx.fol_profile(tab.data_ptr(), rows, prof.data_ptr(), prm_.data_ptr() if perm else 0, cnt.data_ptr(), prm,
+                        st.cuda_stream)
+    st.synchronize()
+    return prof, prm_, cnt
+
+
 def class_kinds(class_id, kind) -> dict:
     """{class id: sorted tuple of the kinds its members carry} for the classified rows
     (``class_id >= 0``); the kind is a property of the class, so a tuple of more than one entry

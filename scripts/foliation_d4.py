@@ -26,7 +26,10 @@ of the rows the complex pass took, the classes still mixed and the time of its l
 and --omega 0,1/2,1 the kinds at each of these rotation rates come from one pdeval_fol_reduce_multi call
 and are reported under "reduce"/"omega": the histogram per Omega, the kinds of each tagged class at each
 Omega, and the call's time next to that of one pdeval_fol_reduce call per value (with --cplx both carry
-PDEVAL_FOL_CPLX).
+PDEVAL_FOL_CPLX).  With --reduce and --profile the table of the accepted rows is integrated by
+pdeval_fol_profile and reported under "reduce"/"profile": per kind the rows that get a profile, per tagged
+class n, the range of u and psi' and Q at the last sample, and the kernel's time next to that of
+torch.sort, gathers and torch.cumsum on the same table (and, under "m64", on 256 rows at m = 64).
 
     python scripts/foliation_d4.py --axis --cplx --reduce --settle --out foliation_d4.json
 """
@@ -63,6 +66,8 @@ def main():
     ap.add_argument('--omega', default=None,
                     help='with --reduce: a comma-separated list of at most 8 rotation rates, e.g. 0,1/2,1: the kinds at '
                          'each of them in one pass (pdeval_fol_reduce_multi)')
+    ap.add_argument('--profile', action='store_true',
+                    help='with --reduce: psi(u) and the current of every accepted row (pdeval_fol_profile)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.repeats < 5:
@@ -282,6 +287,68 @@ def main():
             'qmax_above_tau_min': float(q[q > prm.tau].min(initial=np.inf)),
         }
 
+    def profile(cls, tags, p, rows):
+        """pdeval_fol_profile on the table of the first `rows` accepted rows under parameters p (Omega = 0)
+        against what a caller had before it -- torch.sort on u, gathers and torch.cumsum on the same
+        table: one warm-up run each, then the median of the repeats.  Per kind the rows that get a
+        profile (n >= min_points); per tagged class (rows within the first `rows`) n, the range of u,
+        psi' and Q at the last sample and whether psi' == 1 throughout (the class's u is already psi)."""
+        rows = min(rows, len(acc))
+        mm_ = int(p.m) ** 2
+        kind = torch.zeros(rows, dtype=torch.uint8, device=dev)
+        tab = torch.empty((rows, 3, mm_), dtype=torch.float64, device=dev)
+        prof = torch.empty((rows, 4, mm_), dtype=torch.float64, device=dev)
+        perm = torch.empty((rows, mm_), dtype=torch.int32, device=dev)
+        cnt = torch.empty(rows, dtype=torch.int32, device=dev)
+        with torch.cuda.stream(st):
+            ctx.fol_reduce(d_ops.data_ptr(), ops.size, d_off.data_ptr(), n, d_acc.data_ptr(), rows, kind.data_ptr(), 0.0,
+                           0, 0, tab.data_ptr(), p, st.cuda_stream)
+        st.synchronize()
+
+        def by_torch():
+            ok = torch.isfinite(tab).all(1)
+            u, order = torch.sort(torch.where(ok, tab[:, 0] + 0.0, torch.inf), dim=1, stable=True)
+            ok = torch.gather(ok, 1, order)
+            kap = torch.where(ok, torch.gather(tab[:, 1], 1, order), 0.0)
+            g = torch.where(ok, torch.gather(tab[:, 2], 1, order), 0.0)
+            d = torch.zeros_like(u)
+            d[:, 1:] = torch.where(ok[:, 1:], u[:, 1:] - u[:, :-1], 0.0)
+            mid = lambda f: torch.cat([torch.zeros_like(f[:, :1]), 0.5 * (f[:, 1:] + f[:, :-1])], 1) * d   # noqa: E731
+            dp = torch.exp(torch.cumsum(mid(kap), 1))
+            return u, dp, torch.cumsum(mid(dp), 1), torch.cumsum(mid(g * dp * dp), 1), order, ok.sum(1)
+
+        def call_ms(kernel):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            with torch.cuda.stream(st):
+                e0.record(st)
+                if kernel:
+                    ctx.fol_profile(tab.data_ptr(), rows, prof.data_ptr(), perm.data_ptr(), cnt.data_ptr(), p, st.cuda_stream)
+                else:
+                    by_torch()
+                e1.record(st)
+            st.synchronize()
+            return e0.elapsed_time(e1)
+
+        ms = {}
+        for kernel in (True, False):
+            call_ms(kernel)
+            ms[kernel] = [call_ms(kernel) for _ in range(a.repeats)]
+        k, nn, pr = kind.cpu().numpy(), cnt.cpu().numpy(), prof.cpu().numpy()
+        have = nn >= int(p.min_points)
+        paper = {}
+        for c, name in sorted(tags.items()):
+            for r in np.flatnonzero(cls.class_id[:rows] == c)[:1]:     # the class's first row stands for it
+                last = int(nn[r]) - 1
+                e = paper[f'{name} ({c})'] = {'candidate': int(acc[r]), 'kind': FOL.KIND_NAMES[int(k[r])], 'n': int(nn[r])}
+                if have[r]:
+                    e.update({'u_range': [float(pr[r, 0, 0]), float(pr[r, 0, last])], 'dpsi_last': float(pr[r, 1, last]),
+                              'Q_last': float(pr[r, 3, last]), 'dpsi_is_one': bool((pr[r, 1, :last + 1] == 1.0).all()),
+                              'dpsi_minus_one_max': float(np.abs(pr[r, 1, :last + 1] - 1.0).max())})
+        return {'m': int(p.m), 'rows': rows, 'kernel_ms': statistics.median(ms[True]), 'kernel_ms_all': ms[True],
+                'torch_ms': statistics.median(ms[False]), 'torch_ms_all': ms[False],
+                'rows_with_profile': {FOL.KIND_NAMES[x]: int((have & (k == x)).sum()) for x in range(4)},
+                'paper_profiles': paper}
+
     def reduce_omega(cls, tags, p):
         """The reduction kinds at every Omega of --omega in one pdeval_fol_reduce_multi call against one
         pdeval_fol_reduce call per value, both with counts and qmax and without a table: one warm-up
@@ -343,6 +410,11 @@ def main():
         out['reduce'] = reduce(red_cls, red_tags)
         if a.omega:
             out['reduce']['omega'] = reduce_omega(red_cls, red_tags, fol_params(prm, cplx=a.cplx))
+        if a.profile:
+            out['reduce']['profile'] = profile(red_cls, red_tags, prm, len(acc))
+            big = fol_params(prm)
+            big.m = 64
+            out['reduce']['profile']['m64'] = profile(red_cls, {}, big, 256)
     if a.cplx:
         out['cplx'] = with_cplx(fol_params(prm, axis=False, cplx=True), plain_cls)
         if a.axis:
